@@ -4,7 +4,7 @@
 synthetic (source, target) pairs of length 128, bf16 compute, synchronous data
 parallelism over RCCL on N MI355X GPUs (one process per GPU).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: starts its own N ranks, one per GPU, when no launcher set
     WORLD_SIZE; under python -m torch.distributed.run --nproc-per-node N it
     is one of the N ranks. A world that is not N exits non-zero.)
@@ -14,6 +14,11 @@ backward, bucketed gradient all-reduce, Adam update. Weak scaling: the local
 batch (default 64 sentence pairs per GPU, the reference's local_batch_size,
 configuration/settings.yaml) is fixed, so the global batch is 64*N.
 tokens/step = global_batch * (src_len + tgt_len) = 64*N*256.
+
+A plain run sets up, warms up, times the K steps and prints one JSON line.
+--dump-outputs DIR also writes what the last timed step computed (below);
+--full is where every measurement or check beyond the headline figure goes
+(none today: the headline run already is the whole benchmark).
 """
 from __future__ import annotations
 
@@ -108,6 +113,44 @@ def self_launch(n: int) -> int:
     return launch.launch([os.path.abspath(__file__)] + sys.argv[1:], n, spec, env_extra=extra)
 
 
+# --dump-outputs: at most this many elements of each large array (a fixed,
+# seeded sample beyond it), so the files stay under 64 MB in all
+DUMP_MAX_ELEMS = 6 * 2 ** 20
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_sample_index(n: int):
+    """The elements of a flat buffer of n > DUMP_MAX_ELEMS elements that
+    --dump-outputs writes: sorted indices drawn from a seeded generator, the
+    same in every run and every build (call this to map a dumped element back
+    to its place in the buffer)."""
+    import numpy as np
+
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    return np.sort(rng.integers(0, n, size=DUMP_MAX_ELEMS, dtype=np.int64))
+
+
+def dump_outputs(path: str, step, model) -> None:
+    """Write what the last timed step computed as float32 <name>.npy files:
+
+      step_out  the (loss, accuracy) pair the step returns to its caller
+      params    the fp32 master weights after the step's Adam update
+      grads     the gradients the step left in the flat gradient buffer (GPU;
+                the CPU reference optimizer zeroes them after its update)
+
+    params and grads are one flat buffer each; beyond DUMP_MAX_ELEMS elements
+    the fixed sample dump_sample_index() is written (2 x 24 MB then)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "step_out.npy"), step.last.detach().float().cpu().numpy())
+    for name, flat in (("params", model.store.flat), ("grads", model.store.flat_grad)):
+        flat = flat.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            flat = flat[torch.from_numpy(dump_sample_index(flat.numel())).to(flat.device)]
+        np.save(os.path.join(path, name + ".npy"), flat.float().cpu().numpy())
+
+
 def _fp8_precision() -> str:
     from tensorflow_distributed_on_gke_amd.ops.fp8 import precision_string
     return precision_string()
@@ -140,6 +183,13 @@ def main() -> None:
     ap.add_argument("--verify-replicas", type=int, default=0,
                     help="1: after the timed steps (outside the timing), check that every rank's "
                          "weights are bitwise equal (DataParallel.verify_replicas; exits non-zero if not)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (its "
+                         "returned loss/accuracy, the updated weights, the gradients) as float32 "
+                         "DIR/<name>.npy, at most 64 MB in all (rank 0; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures or checks beyond the headline "
+                         "figure (nothing today: a plain run is the whole benchmark)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -228,6 +278,8 @@ def main() -> None:
     tokens = global_batch * (S + T) * args.steps
     value = tokens / elapsed
     loss = float(step.last[0].item()) * world if dev.type == "cuda" else float(step.last[0])
+    if args.dump_outputs and info.rank == 0:
+        dump_outputs(args.dump_outputs, step, model)
     if info.rank == 0:
         print(json.dumps({
             "metric": METRIC,

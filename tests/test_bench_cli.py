@@ -85,6 +85,74 @@ def test_bench_self_launches_eight_ranks():
     assert r.stderr.count("comm_issue=thread") == 8  # every rank on the thread path
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """`--dump-outputs DIR` writes what the last timed step computed as float32
+    .npy files within 64 MB; the same arguments give the same inputs, so two
+    runs (one with --full, which adds nothing to the result line's meaning)
+    write the same arrays. --steps sets the number of timed steps."""
+    import numpy as np
+
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        out = tmp_path / name
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1",
+               "--preset", "tiny", "--local-batch", "4", "--seq-len", "16",
+               "--dump-outputs", str(out)] + extra
+        env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK",
+                                                                "MASTER_ADDR", "MASTER_PORT")}
+        env["OMP_NUM_THREADS"] = "2"
+        r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["unit"] == "tokens/s"
+        expect = 4 * (16 + 16) / (d["ms_per_step"] / 1000.0)
+        assert abs(d["value"] - expect) / expect < 0.01
+        files = sorted(os.listdir(out))
+        assert {"step_out.npy", "params.npy", "grads.npy"} <= set(files)
+        assert all(f.endswith(".npy") for f in files)
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 * 2 ** 20
+        arrs = {f: np.load(out / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert np.isfinite(arrs["params.npy"]).all() and arrs["step_out.npy"].shape == (2,)
+        assert abs(float(arrs["step_out.npy"][0]) - d["config"]["last_loss"]) < 1e-3
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
+def test_dump_outputs_samples_large_buffers(tmp_path, monkeypatch):
+    """A flat buffer beyond the element limit is written as a fixed seeded
+    sample (sorted indices, the same every time: dump_sample_index)."""
+    import importlib.util
+    import types
+
+    import numpy as np
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    # two sampled float32 buffers, the step's pair and the .npy headers: within 64 MB
+    assert 2 * bench.DUMP_MAX_ELEMS * 4 + 4096 <= 64 * 2 ** 20
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 100)
+    flat = torch.arange(1000, dtype=torch.float32)
+    model = types.SimpleNamespace(store=types.SimpleNamespace(flat=flat, flat_grad=-flat[:50]))
+    step = types.SimpleNamespace(last=torch.tensor([2.5, 0.25]))
+    bench.dump_outputs(str(tmp_path / "a"), step, model)
+    bench.dump_outputs(str(tmp_path / "b"), step, model)
+    a = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    b = {f: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+    assert sorted(a) == ["grads.npy", "params.npy", "step_out.npy"]
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+    idx = bench.dump_sample_index(1000)
+    assert idx.shape == (100,) and (np.diff(idx) >= 0).all() and idx.min() >= 0 and idx.max() < 1000
+    assert np.array_equal(a["params.npy"], idx.astype(np.float32))  # flat[i] == i
+    assert np.array_equal(a["grads.npy"], -np.arange(50, dtype=np.float32))  # small: whole
+
+
 def test_visible_gpus_does_not_initialise_hip(monkeypatch):
     """The self-launching parent counts GPUs from the visible-devices lists
     or the KFD topology, never through a HIP call."""
