@@ -98,12 +98,18 @@ int tdg_xent_stats(const float* row_loss, const float* row_correct, int M, const
 int tdg_adam(float* p, float* g, float* m, float* v, void* shadow, long long n, long long* step,
              float beta1, float beta2, float eps, float lr_const, float d_model, float warmup,
              float grad_scale, float weight_decay, int sched, int zero_grad, int inc_step,
-             hipStream_t st);
+             const float* gstate, hipStream_t st);
 int tdg_adam_chunks(float* p, float* g, float* m, float* v, void* shadow, long long n,
                     const void* chunks, int nchunks, long long* step, float beta1, float beta2,
                     float eps, float lr_const, float d_model, float warmup, float grad_scale,
                     float weight_decay, int sched, int zero_grad, int inc_step,
-                    const float* scale8, unsigned* amax8, hipStream_t st);
+                    const float* scale8, unsigned* amax8, const float* gstate, hipStream_t st);
+int tdg_adam_step_inc(long long* step, const float* gstate, hipStream_t st);
+long long tdg_grad_sumsq(const float* g, const void* chunks, long long nchunks, long long n,
+                         float* partials, hipStream_t st);
+int tdg_grad_norm_finalize(const float* partials, long long nparts, float* state,
+                           unsigned* counters, float clip, int skip_on, float grad_scale,
+                           hipStream_t st);
 int tdg_to_bf16(const float* p, void* o, long long n, hipStream_t st);
 int tdg_transpose_grouped(const void* const* src, void* const* dst, int G, int R, int C,
                           hipStream_t st);
@@ -1491,10 +1497,21 @@ void xent_stats(const Tensor& row_loss, const Tensor& row_correct, const Tensor&
 }
 
 // ---------------------------------------------------------------- optimizer
+// The device state of the gradient-norm pass (grad_norm_finalize), or null.
+static const float* norm_state_ptr(const optional<Tensor>& gstate, const Tensor& like) {
+  if (!gstate.has_value()) return nullptr;
+  check_f32(*gstate, "norm state");
+  TORCH_CHECK(gstate->is_cuda() && gstate->device() == like.device() && gstate->is_contiguous() &&
+                  gstate->numel() >= 4,
+              "norm state: >= 4 contiguous f32 on the gradient's GPU");
+  return gstate->data_ptr<float>();
+}
+
 void adam(const Tensor& p, const Tensor& g, const Tensor& m, const Tensor& v,
           const optional<Tensor>& shadow, const Tensor& step, double beta1, double beta2,
           double eps, double lr_const, double d_model, double warmup, double grad_scale,
-          double weight_decay, int64_t sched, bool zero_grad, bool inc_step) {
+          double weight_decay, int64_t sched, bool zero_grad, bool inc_step,
+          const optional<Tensor>& gstate) {
   for (auto* t : {&p, &g, &m, &v}) {
     check_f32(*t, "adam buffers");
     check_contig(*t, "adam buffers");
@@ -1511,7 +1528,8 @@ void adam(const Tensor& p, const Tensor& g, const Tensor& m, const Tensor& v,
                      v.data_ptr<float>(), shadow.has_value() ? shadow->data_ptr() : nullptr,
                      p.numel(), reinterpret_cast<long long*>(step.data_ptr<int64_t>()), (float)beta1, (float)beta2, (float)eps,
                      (float)lr_const, (float)d_model, (float)warmup, (float)grad_scale,
-                     (float)weight_decay, (int)sched, zero_grad, inc_step, stream_of(p)),
+                     (float)weight_decay, (int)sched, zero_grad, inc_step,
+                     norm_state_ptr(gstate, p), stream_of(p)),
             "tdg adam");
 }
 
@@ -1522,7 +1540,8 @@ void adam_chunks(const Tensor& p, const Tensor& g, const Tensor& m, const Tensor
                  const Tensor& shadow, const Tensor& chunks, const Tensor& step, double beta1,
                  double beta2, double eps, double lr_const, double d_model, double warmup,
                  double grad_scale, double weight_decay, int64_t sched, bool zero_grad,
-                 bool inc_step, const Tensor& scale8, const Tensor& amax8) {
+                 bool inc_step, const Tensor& scale8, const Tensor& amax8,
+                 const optional<Tensor>& gstate) {
   for (auto* t : {&p, &g, &m, &v}) {
     check_f32(*t, "adam buffers");
     check_contig(*t, "adam buffers");
@@ -1551,8 +1570,73 @@ void adam_chunks(const Tensor& p, const Tensor& g, const Tensor& m, const Tensor
                             (float)beta1, (float)beta2, (float)eps, (float)lr_const, (float)d_model,
                             (float)warmup, (float)grad_scale, (float)weight_decay, (int)sched,
                             zero_grad, inc_step, scale8.data_ptr<float>(),
-                            reinterpret_cast<unsigned*>(amax8.data_ptr()), stream_of(p)),
+                            reinterpret_cast<unsigned*>(amax8.data_ptr()),
+                            norm_state_ptr(gstate, p), stream_of(p)),
             "tdg adam_chunks");
+}
+
+void adam_step_inc(const Tensor& step, const optional<Tensor>& gstate) {
+  TORCH_CHECK(step.scalar_type() == at::kLong && step.is_cuda(), "adam: step int64 GPU");
+  c10::DeviceGuard gd(step.device());
+  check_err(tdg_adam_step_inc(reinterpret_cast<long long*>(step.data_ptr<int64_t>()),
+                              norm_state_ptr(gstate, step), stream_of(step)),
+            "tdg adam_step_inc");
+}
+
+// partials[base ..) = one squared sum per <= 4096-element chunk of g: the
+// chunks of an Adam chunk table [n, 4] int64 (whose contents were validated
+// where it was built, as for adam_chunks), or without a table the
+// consecutive 4096-element pieces of g (numel % 4 == 0). Returns how many
+// partials were written.
+int64_t grad_sumsq(const Tensor& g, const optional<Tensor>& chunks, const Tensor& partials,
+                   int64_t base) {
+  check_f32(g, "grad_sumsq gradient");
+  check_contig(g, "grad_sumsq gradient");
+  check_f32(partials, "grad_sumsq partials");
+  check_contig(partials, "grad_sumsq partials");
+  TORCH_CHECK(g.is_cuda() && partials.device() == g.device(), "grad_sumsq: GPU tensors");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(g.data_ptr()) % 16 == 0,
+              "grad_sumsq: gradient range must start 16-byte aligned");
+  int64_t nch;
+  const void* tab = nullptr;
+  if (chunks.has_value()) {
+    TORCH_CHECK(chunks->is_cuda() && chunks->scalar_type() == at::kLong && chunks->dim() == 2 &&
+                    chunks->size(1) == 4 && chunks->is_contiguous(),
+                "grad_sumsq: chunk table [n, 4] int64 on the GPU");
+    nch = chunks->size(0);
+    TORCH_CHECK(nch >= 1 && nch <= (g.numel() + 3) / 4,
+                "grad_sumsq: chunk count out of range for the gradient buffer");
+    tab = chunks->data_ptr();
+  } else {
+    TORCH_CHECK(g.numel() > 0 && g.numel() % 4 == 0, "grad_sumsq: length must be a multiple of 4");
+    nch = (g.numel() + 4095) / 4096;
+  }
+  TORCH_CHECK(base >= 0 && base + nch <= partials.numel(), "grad_sumsq: partials buffer too small");
+  c10::DeviceGuard gd(g.device());
+  const long long r = tdg_grad_sumsq(g.data_ptr<float>(), tab, nch, g.numel(),
+                                     partials.data_ptr<float>() + base, stream_of(g));
+  TORCH_CHECK(r == nch, "tdg grad_sumsq failed");
+  return nch;
+}
+
+// state (f32 [>= 4]: squared sum, norm, clip factor, skip flag) and counters
+// (int32 [>= 4]: steps clipped, steps skipped, bits of the largest finite
+// norm) from partials[0 .. nparts).
+void grad_norm_finalize(const Tensor& partials, int64_t nparts, const Tensor& state,
+                        const Tensor& counters, double clip, bool skip_on, double grad_scale) {
+  check_f32(partials, "grad_norm_finalize partials");
+  check_contig(partials, "grad_norm_finalize partials");
+  TORCH_CHECK(nparts >= 0 && nparts <= partials.numel(), "grad_norm_finalize: partial count");
+  TORCH_CHECK(counters.is_cuda() && counters.scalar_type() == at::kInt && counters.is_contiguous() &&
+                  counters.numel() >= 4 && counters.device() == partials.device(),
+              "grad_norm_finalize: counters int32 [>= 4] on the GPU");
+  const optional<Tensor> st(state);
+  float* sp = const_cast<float*>(norm_state_ptr(st, partials));
+  c10::DeviceGuard gd(partials.device());
+  check_err(tdg_grad_norm_finalize(partials.data_ptr<float>(), nparts, sp,
+                                   reinterpret_cast<unsigned*>(counters.data_ptr<int>()),
+                                   (float)clip, skip_on, (float)grad_scale, stream_of(partials)),
+            "tdg grad_norm_finalize");
 }
 
 // dsts[g] [C, R] = srcs[g] [R, C]^T (bf16, same shape, <= 64 matrices, one launch)
@@ -1690,6 +1774,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xent_stats", &xent_stats);
   m.def("adam", &adam);
   m.def("adam_chunks", &adam_chunks);
+  m.def("adam_step_inc", &adam_step_inc);
+  m.def("grad_sumsq", &grad_sumsq);
+  m.def("grad_norm_finalize", &grad_norm_finalize);
   m.def("reduce_partials_multi", &reduce_partials_multi);
   m.def("to_bf16", &to_bf16);
   m.attr("ARCH") = "gfx950";

@@ -12,6 +12,11 @@
 // the optimizer step needs no host sync and can be captured in a HIP graph.
 // Fused: bf16 shadow-weight refresh (the compute copy the GEMMs read) and
 // zeroing of the consumed gradient (so backward can accumulate).
+//
+// Optional global-norm clipping / non-finite step skip (Keras global_clipnorm,
+// tf.clip_by_global_norm): grad_sumsq_kernel + grad_norm_finalize_kernel leave
+// the decision in a small device state (GNS_*), which the Adam kernels read
+// through a nullable pointer -- null: exactly the unclipped update.
 #include "tdg_common.h"
 
 namespace tdg {
@@ -26,6 +31,20 @@ struct AdamCfg {
   int sched;          // 0 const, 1 noam
   int zero_grad;
 };
+
+// Device state written by grad_norm_finalize_kernel (f32 words) ...
+enum { GNS_SUMSQ = 0, GNS_NORM = 1, GNS_FACTOR = 2, GNS_SKIP = 3, GNS_WORDS = 4 };
+// ... and its counters (32-bit words; the maximum is the bit pattern of a
+// non-negative float, which orders like the integer).
+enum { GNC_CLIPPED = 0, GNC_SKIPPED = 1, GNC_MAXNORM = 2, GNC_WORDS = 4 };
+
+// The step's clip factor folded into grad_scale (factor 1.0f: the same bits
+// as without a state); true when the step is to be skipped.
+__device__ __forceinline__ bool apply_norm_state(AdamCfg& c, const float* __restrict__ gstate) {
+  if (!gstate) return false;
+  c.grad_scale *= gstate[GNS_FACTOR];
+  return gstate[GNS_SKIP] != 0.f;
+}
 
 __device__ __forceinline__ float noam_lr(const AdamCfg& c, float step) {
   if (c.sched == 0) return c.lr_const;
@@ -82,7 +101,17 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
                                                    float* __restrict__ m, float* __restrict__ v,
                                                    bf16_t* __restrict__ shadow, long long n,
                                                    const long long* __restrict__ step_ptr,
-                                                   AdamCfg c) {
+                                                   AdamCfg c, const float* __restrict__ gstate) {
+  const bool skip = apply_norm_state(c, gstate);
+  if (skip) {  // non-finite gradient: nothing but the gradient zeroing
+    if (c.zero_grad) {
+      float4* G4 = reinterpret_cast<float4*>(g);
+      const long long stride = (long long)gridDim.x * blockDim.x;
+      for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (n >> 2); i += stride)
+        G4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    return;
+  }
   const float step = (float)step_ptr[0];
   const float t = step + 1.f;
   const float lr = noam_lr(c, step);
@@ -131,8 +160,16 @@ __global__ __launch_bounds__(256) void adam_chunk_kernel(
     float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
     bf16_t* __restrict__ shadow, long long n, const AdamChunk* __restrict__ chunks,
     const long long* __restrict__ step_ptr, AdamCfg c, const float* __restrict__ scale8,
-    unsigned* __restrict__ amax8) {
+    unsigned* __restrict__ amax8, const float* __restrict__ gstate) {
   const AdamChunk ch = chunks[blockIdx.x];
+  if (apply_norm_state(c, gstate)) {  // skipped step: no weight, moment, shadow, e4m3 or amax write
+    if (c.zero_grad) {
+      float4* G4 = reinterpret_cast<float4*>(g);
+      for (long long j = threadIdx.x; j < ch.n / 4; j += 256)
+        G4[ch.start / 4 + j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    return;
+  }
   const float step = (float)step_ptr[0];
   const float t = step + 1.f;
   const float lr = noam_lr(c, step);
@@ -186,7 +223,87 @@ __global__ __launch_bounds__(256) void adam_chunk_kernel(
   }
 }
 
-__global__ void step_inc_kernel(long long* step) { step[0] += 1; }
+// (a skipped step advances neither the Noam schedule nor the bias correction)
+__global__ void step_inc_kernel(long long* step, const float* __restrict__ gstate) {
+  if (gstate && gstate[GNS_SKIP] != 0.f) return;
+  step[0] += 1;
+}
+
+// Squared sum of a gradient range, one f32 partial per <= 4096-element chunk:
+// one workgroup per chunk, <= 4 16-byte loads per thread issued together,
+// <= 16 sequential f32 adds per thread, DPP wave sum, 4-wave combine through
+// LDS. No atomics and no grid-dependent order: bitwise reproducible. Chunks
+// come from an AdamChunk table, or (chunks == nullptr) are the consecutive
+// 4096-element pieces of g[0, n), n % 4 == 0. Pure HBM read: 4 B/parameter.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g,
+                                                         const AdamChunk* __restrict__ chunks,
+                                                         long long n, float* __restrict__ partials) {
+  long long i0, n4;
+  if (chunks) {
+    const AdamChunk ch = chunks[blockIdx.x];
+    i0 = ch.start / 4;
+    n4 = ch.n / 4;
+  } else {
+    const long long c0 = (long long)blockIdx.x * ADAM_CHUNK;
+    i0 = c0 / 4;
+    n4 = (n - c0 < ADAM_CHUNK ? n - c0 : (long long)ADAM_CHUNK) / 4;
+  }
+  const float4* G4 = reinterpret_cast<const float4*>(g);
+  float4 ga[ADAM_PER_THREAD];
+#pragma unroll
+  for (int k = 0; k < ADAM_PER_THREAD; ++k) {
+    const long long j = threadIdx.x + 256 * k;
+    ga[k] = j < n4 ? G4[i0 + j] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < ADAM_PER_THREAD; ++k) {
+    s += ga[k].x * ga[k].x;
+    s += ga[k].y * ga[k].y;
+    s += ga[k].z * ga[k].z;
+    s += ga[k].w * ga[k].w;
+  }
+  __shared__ float red[4];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// One workgroup: the partials summed in double in a fixed order (thread t
+// takes partials t, t + 256, ... in index order, then a fixed LDS tree), the
+// norm of the scaled gradient, tf.clip_by_global_norm's factor
+// clip / max(norm, clip) (exactly 1.0f when norm <= clip; NaN for a
+// non-finite norm that is not skipped, as TF signals it), the skip flag, and
+// the counters. clip <= 0: no clipping (factor 1).
+__global__ __launch_bounds__(256) void grad_norm_finalize_kernel(
+    const float* __restrict__ partials, long long nparts, float* __restrict__ state,
+    unsigned* __restrict__ counters, float clip, int skip_on, float grad_scale) {
+  __shared__ double red[256];
+  double s = 0.0;
+  for (long long i = threadIdx.x; i < nparts; i += 256) s += (double)partials[i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+#pragma unroll
+  for (int w = 128; w >= 1; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  const double sumsq = red[0] * (double)grad_scale * (double)grad_scale;
+  const float norm = (float)sqrt(sumsq);
+  const bool finite = isfinite(norm);
+  const bool skip = skip_on && !finite;
+  float factor = 1.f;
+  if (clip > 0.f && !skip) factor = finite ? clip / fmaxf(norm, clip) : __builtin_nanf("");
+  state[GNS_SUMSQ] = (float)sumsq;
+  state[GNS_NORM] = norm;
+  state[GNS_FACTOR] = factor;
+  state[GNS_SKIP] = skip ? 1.f : 0.f;
+  if (finite && clip > 0.f && norm > clip) counters[GNC_CLIPPED] += 1u;
+  if (skip) counters[GNC_SKIPPED] += 1u;
+  if (finite) counters[GNC_MAXNORM] = max(counters[GNC_MAXNORM], __float_as_uint(norm));
+}
 
 // p_bf16 = bf16(p_f32) for the whole flat buffer (init / checkpoint load).
 __global__ void to_bf16_kernel(const float* __restrict__ p, bf16_t* __restrict__ o, long long n) {
@@ -263,7 +380,8 @@ extern "C" int tdg_transpose_grouped(const void* const* src, void* const* dst, i
 extern "C" int tdg_adam(float* p, float* g, float* m, float* v, void* shadow, long long n,
                         long long* step, float beta1, float beta2, float eps, float lr_const,
                         float d_model, float warmup, float grad_scale, float weight_decay,
-                        int sched, int zero_grad, int inc_step, hipStream_t st) {
+                        int sched, int zero_grad, int inc_step, const float* gstate,
+                        hipStream_t st) {
   if (n % 4 != 0) return -1;
   AdamCfg c{beta1, beta2, eps, lr_const, d_model, warmup, grad_scale, weight_decay, sched,
             zero_grad};
@@ -275,10 +393,10 @@ extern "C" int tdg_adam(float* p, float* g, float* m, float* v, void* shadow, lo
     const long long n4 = cn / 4;
     const int blocks = (int)std::min<long long>(8192, (n4 + 255) / 256);
     hipLaunchKernelGGL(adam_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, p + o, g + o,
-                       m + o, v + o, shadow ? (bf16_t*)shadow + o : nullptr, cn, step, c);
+                       m + o, v + o, shadow ? (bf16_t*)shadow + o : nullptr, cn, step, c, gstate);
   }
   // per-bucket updates (data parallel) share one step: only the last advances it
-  if (inc_step) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, st, step);
+  if (inc_step) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, st, step, gstate);
   return 0;
 }
 
@@ -290,13 +408,44 @@ extern "C" int tdg_adam_chunks(float* p, float* g, float* m, float* v, void* sha
                                float beta2, float eps, float lr_const, float d_model, float warmup,
                                float grad_scale, float weight_decay, int sched, int zero_grad,
                                int inc_step, const float* scale8, unsigned* amax8,
-                               hipStream_t st) {
+                               const float* gstate, hipStream_t st) {
   if (n % 4 != 0 || n >= (1LL << 28) || nchunks <= 0) return -1;
   AdamCfg c{beta1, beta2, eps, lr_const, d_model, warmup, grad_scale, weight_decay, sched,
             zero_grad};
   hipLaunchKernelGGL(adam_chunk_kernel, dim3(nchunks), dim3(256), 0, st, p, g, m, v,
-                     (bf16_t*)shadow, n, (const AdamChunk*)chunks, step, c, scale8, amax8);
-  if (inc_step) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, st, step);
+                     (bf16_t*)shadow, n, (const AdamChunk*)chunks, step, c, scale8, amax8, gstate);
+  if (inc_step) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, st, step, gstate);
+  return 0;
+}
+
+// Keras `iterations += 1` for a step applied as several ranges (gstate: not
+// on a skipped step).
+extern "C" int tdg_adam_step_inc(long long* step, const float* gstate, hipStream_t st) {
+  hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, st, step, gstate);
+  return 0;
+}
+
+// partials[0 .. nchunks) = squared sums of the table's chunks of g, or
+// (chunks == nullptr) of the ceil(n / 4096) consecutive pieces of g[0, n).
+// Returns the number of partials written, or -1.
+extern "C" long long tdg_grad_sumsq(const float* g, const void* chunks, long long nchunks,
+                                    long long n, float* partials, hipStream_t st) {
+  if (!chunks) {
+    if (n <= 0 || n % 4 != 0) return -1;
+    nchunks = (n + ADAM_CHUNK - 1) / ADAM_CHUNK;
+  }
+  if (nchunks <= 0 || nchunks > 0x7fffffffLL) return -1;
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)nchunks), dim3(256), 0, st, g,
+                     (const AdamChunk*)chunks, n, partials);
+  return nchunks;
+}
+
+extern "C" int tdg_grad_norm_finalize(const float* partials, long long nparts, float* state,
+                                      unsigned* counters, float clip, int skip_on,
+                                      float grad_scale, hipStream_t st) {
+  if (nparts < 0) return -1;
+  hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, st, partials, nparts, state,
+                     counters, clip, skip_on, grad_scale);
   return 0;
 }
 

@@ -45,6 +45,12 @@ class Settings:
     beta2: float = 0.98
     epsilon: float = 1e-9
     learning_rate: Optional[float] = None  # None -> Noam schedule
+    # extensions, off by default (the reference sets neither): Keras Adam's
+    # global_clipnorm (tf.clip_by_global_norm over the whole all-reduced
+    # gradient; 0: off) and skipping of steps whose gradient norm is inf / NaN
+    # (weights, moments and `iterations` untouched)
+    global_clipnorm: float = 0.0
+    skip_nonfinite: bool = False
     # --- loop (reference __main__.py:89, 149-180)
     epochs: int = 20
     steps_per_epoch: int = 200

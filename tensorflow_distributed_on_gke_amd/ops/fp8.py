@@ -633,5 +633,25 @@ class Fp8State:
         self.meta.update()
         self.gmeta.update()
 
+    def hold_weight_scales(self) -> torch.Tensor:
+        """The scales as they are, for keep_weight_scales_if()."""
+        return self.meta.scale.clone()
+
+    def keep_weight_scales_if(self, held: torch.Tensor, skip_flag: torch.Tensor) -> None:
+        """After a fused optimizer step that may have been skipped on device
+        (Adam skip_nonfinite; skip_flag: its one-element state word): a
+        skipped step left the e4m3 weight copies untouched, so the weight
+        slots get back the scales those copies were written with (`held`,
+        taken before before_fused_opt()). The activation and gradient scales
+        keep advancing. No host read."""
+        mask, nslots = getattr(self, "_wslot_mask", (None, -1))
+        if nslots != len(self.meta.names):  # (slots are all named by the first eager step)
+            mask = torch.zeros(self.meta.scale.numel(), dtype=torch.bool)
+            for i, n in enumerate(self.meta.names):
+                mask[i] = n.startswith(("w:", "wt:"))
+            mask = mask.to(self.meta.scale.device)
+            self._wslot_mask = (mask, len(self.meta.names))
+        self.meta.scale.copy_(torch.where(mask & (skip_flag != 0), held, self.meta.scale))
+
 
 load_tuned(TUNED_FILE)

@@ -247,11 +247,15 @@ class DataParallel:
         updates buckets mid-backward, once the model passed a release point
         (ParamStore.release_point: no later backward kernel reads those
         weights) -- the decoder side during the encoder's backward. The
-        optimizer must offer apply_range(start, end, inc_step) / advance_step()."""
+        optimizer must offer apply_range(start, end, inc_step) / advance_step().
+        An optimizer that clips by the global norm or skips non-finite steps
+        (opt.clip_on) needs the norm of the whole reduced gradient before any
+        span's update: no mid-backward updates (release is ignored), and
+        finish() runs the norm pass first (accumulate_norm / finalize_norm)."""
         if not self.active:
             return
         self.opt = opt
-        if release:
+        if release and not getattr(opt, "clip_on", False):
             if self.store.flat.is_cuda:
                 self._upd_stream = torch.cuda.Stream(self.store.flat.device)
             self.store.on_release(self._on_release)
@@ -507,15 +511,28 @@ class DataParallel:
         # of the first group runs while those two all-reduces are in flight
         # (and while the host thread issues them: the first wait does not
         # block the host on a span issued moments ago).
+        # Clipping / skipping (opt.clip_on): what overlaps the last two
+        # all-reduces is the first group's share of the norm pass (the squared
+        # sums of its spans, of the SUMMED gradient: every rank gets the same
+        # factor); the norm is finalized once every span is in, and only then
+        # does any span's Adam run.
         todo = [b for b in self.buckets if not b.updated]
         cut = -2 if len(todo) >= 3 else -1
+        clip = self.opt is not None and getattr(self.opt, "clip_on", False)
         for grp in (todo[:cut], todo[cut:]):
             if not grp:
                 continue
             self._complete_many(grp)
             if self.opt is not None:
                 for b in grp:
-                    self.opt.apply_range(b.start, b.end, inc_step=False)
+                    if clip:
+                        self.opt.accumulate_norm(b.start, b.end)
+                    else:
+                        self.opt.apply_range(b.start, b.end, inc_step=False)
+        if clip:
+            self.opt.finalize_norm()
+            for b in todo:
+                self.opt.apply_range(b.start, b.end, inc_step=False)
         if self.opt is not None:
             self.opt.advance_step()
         self.reset()

@@ -98,7 +98,8 @@ class Trainer:
             raise ValueError(f"unknown data source {s.data!r} (synthetic | text)")
         self.model = build_model(s, info.device)
         self.opt = Adam(self.model.store, self.model.cfg.d_model, warmup=s.warmup_steps, beta1=s.beta1,
-                        beta2=s.beta2, eps=s.epsilon, lr=s.learning_rate)
+                        beta2=s.beta2, eps=s.epsilon, lr=s.learning_rate,
+                        global_clipnorm=s.global_clipnorm, skip_nonfinite=s.skip_nonfinite)
         comm = torch.bfloat16 if s.grad_comm_dtype == "bf16" else None
         self.ddp = (DataParallel(self.model.store, bucket_mb=s.bucket_mb, comm_dtype=comm)
                     if info.world > 1 else None)
@@ -198,6 +199,18 @@ class Trainer:
             self._quiet("metrics all-reduce")
             dist.all_reduce(t)
         return t.cpu()
+
+    def _clip_record(self) -> Dict[str, float]:
+        """Extra fields of a `train` / `epoch` record with global_clipnorm or
+        skip_nonfinite on (none with both off): the last step's gradient norm,
+        the largest since the previous record, and the steps clipped and
+        skipped so far. Read at log points, where the host has synced."""
+        if not self.opt.clip_on:
+            return {}
+        c = self.opt.clip_counters()
+        self.opt.reset_norm_max()
+        return {"grad_norm": self.opt.last_grad_norm(), "grad_norm_max": c["grad_norm_max"],
+                "clipped_steps": c["clipped_steps"], "skipped_steps": c["skipped_steps"]}
 
     def _to_dev(self, batch):
         dev = self.info.device
@@ -321,7 +334,7 @@ class Trainer:
                                      f"replays {gs['replays']})")
                         self.metrics.write(kind="train", epoch=epoch + 1, batch=batch, step=self.global_step,
                                            loss=float(a[0]) / n, accuracy=float(a[1]) / (n * self._acc_div),
-                                           **st)
+                                           **st, **self._clip_record())
             a = self._reduce(self.step_fn.accum)
             n = max(float(a[2]) / info.world, 1.0)
             train_loss = float(a[0]) / n
@@ -340,7 +353,7 @@ class Trainer:
                             epoch_tokens / max(train_time, 1e-9))
             self.history.append(st)
             self.timer.drain()
-            self.metrics.write(kind="epoch", **st.__dict__)
+            self.metrics.write(kind="epoch", **st.__dict__, **self._clip_record())
             if info.chief:
                 self.log(f"Epoch {epoch + 1} Loss {train_loss:.4f} Accuracy {train_acc:.4f} "
                          f"Test Loss {val['loss']:.4f} Test Accuracy {val['acc']:.4f}")

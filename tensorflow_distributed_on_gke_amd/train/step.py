@@ -3,7 +3,8 @@ graph.
 
 step = dropout-stream advance -> teacher-forced forward -> fused CE/accuracy ->
 backward (gradients into the flat buffer, bucketed RCCL all-reduce started
-from inside backward) -> wait for the buckets -> multi-tensor Adam.
+from inside backward) -> wait for the buckets -> [gradient-norm pass, with
+Adam's global_clipnorm / skip_nonfinite] -> multi-tensor Adam.
 
 Reference: distributed_training_transformer/__main__.py:105-132 (train_step
 inside strategy.run, apply_gradients all-reduce, strategy.reduce(SUM) of the
@@ -104,7 +105,9 @@ class TrainStep:
         # Adam stays on; the mid-backward variant would update weights the
         # fp8 copies of which the encoder backward still reads)
         if ddp is not None and ddp.active and mode != "0" and not (fp8_state is not None and mode != "tail"):
-            ddp.attach_optimizer(opt, release=mode != "tail")
+            # (clipping / skipping: no span's Adam before the norm of the whole
+            # reduced gradient is known, so mid-backward "1" behaves as "tail")
+            ddp.attach_optimizer(opt, release=mode != "tail" and not opt.clip_on)
         # metric accumulators [sum loss, sum acc, n steps, n tokens] (device)
         self.accum = torch.zeros(4, dtype=torch.float32, device=dev)
         self.last = torch.zeros(2, dtype=torch.float32, device=dev)
@@ -153,13 +156,15 @@ class TrainStep:
               self.accum, self.last]
         if self.fp8 is not None:
             ts += [self.fp8.meta.scale, self.fp8.gmeta.scale]
+        if self.opt.clip_on:
+            ts += [self.opt.norm_state, self.opt.norm_counters]
         return ts
 
     def snapshot(self):
         st = [t.clone() for t in self._state()]
         if self.fp8 is not None:
             st += [self.fp8.meta.amax.clone(), self.fp8.gmeta.amax.clone()]
-        return st
+        return st  # (restore() reads the two amax tables from the end)
 
     def restore(self, st) -> None:
         """Put back a snapshot(): weights (and their derived bf16 / transposed /
@@ -178,17 +183,27 @@ class TrainStep:
                                      step_out=self.last, bump_ctr=True, ntok_sum=self._ntok_sum)
         if self.ddp is not None:
             self.ddp.finish()
+        self.optimize()
+        return self.last
+
+    def optimize(self) -> None:
+        """The step after backward and ddp.finish(): the optimizer (unless
+        finish() already ran it per span) and the fp8 bookkeeping."""
         if self.ddp is None or self.ddp.opt is None:
             if self.fp8 is not None and FUSED_FP8_ADAM and \
                     self.fp8.weights.adam_chunks(self.model.store) is not None:
-                # new scales, then Adam refreshing the e4m3 weight copies
+                # new scales, then [the norm pass and] Adam refreshing the
+                # e4m3 weight copies -- which a skipped step leaves alone, so
+                # the weight slots then keep the scales of those copies
+                held = self.fp8.hold_weight_scales() if self.opt.skip_nonfinite else None
                 self.fp8.before_fused_opt()
                 self.opt.apply(fp8w=self.fp8.weights)
-                return self.last
-            self.opt.apply()
+                if held is not None:
+                    self.fp8.keep_weight_scales_if(held, self.opt.norm_state[K.NORM_SKIP:K.NORM_SKIP + 1])
+                return
+            self.opt.apply()  # [the norm pass and] Adam
         if self.fp8 is not None:
             self.fp8.after_step()  # new scales, then fp8 weight copies
-        return self.last
 
     # ------------------------------------------------------------------ HIP graph
     def capture(self, src: torch.Tensor, tgt: torch.Tensor, warmup: int = 2) -> bool:
