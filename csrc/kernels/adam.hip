@@ -17,6 +17,7 @@
 // tf.clip_by_global_norm): grad_sumsq_kernel + grad_norm_finalize_kernel leave
 // the decision in a small device state (GNS_*), which the Adam kernels read
 // through a nullable pointer -- null: exactly the unclipped update.
+#include "tdg_api.h"
 #include "tdg_common.h"
 
 namespace tdg {

@@ -21,6 +21,7 @@
 // Backward: two kernels (dK/dV with key rows on lanes, dQ with query rows on
 // lanes), each recomputing P from the forward's log-sum-exp; no atomics, so
 // gradients are bitwise deterministic.
+#include "tdg_api.h"
 #include "tdg_common.h"
 #include "tdg_attn.h"
 

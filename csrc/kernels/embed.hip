@@ -6,6 +6,7 @@
 // (Embedding -> *sqrt(d) -> +PE[:L] -> Dropout). The PE table is computed once
 // at model build (f32, [max_len, d], as the reference does) and read here; it
 // stays L2-resident.
+#include "tdg_api.h"
 #include "tdg_common.h"
 #include "tdg_ln.h"
 

@@ -24,6 +24,7 @@
 // Replaces (in the fp8 configuration, BASELINE config 5) the forward Dense
 // MatMuls of the reference (distributed_training_transformer/
 // transformer_model.py:119-122, 165, 172-174); backward stays bf16.
+#include "tdg_api.h"
 #include "tdg_common.h"
 #include "tdg_reduce.h"
 

@@ -4,24 +4,10 @@
 // Replaces the reference's Keras Dense MatMul+BiasAdd(+Relu) ops
 // (reference: distributed_training_transformer/transformer_model.py:119-122,
 // 165, 172-174, 333) and their gradients.
+#include "tdg_api.h"
 #include "gemm_impl.h"
 
 namespace tdg {
-#define TDG_DECL(NAME)                                                                          \
-  int gemm_##NAME(int epi, bool f32, int tile_cfg, const bf16_t* A, const bf16_t* B, void* C,    \
-                  const float* bias, const bf16_t* aux, int M, int N, int K, int lda, int ldb,     \
-                  int ldc, int ldaux, float alpha, float beta, int splits, float* ws,              \
-                  hipStream_t st);                                                               \
-  int gemm_grouped_##NAME(const GemmGroup& g, int G, int M, int N, int K, int lda, int ldb,       \
-                          int ldc, bool f32, float alpha, float beta, int tile_cfg,              \
-                          hipStream_t st);                                                       \
-  int gemm_ragged_##NAME(const R256Args& args, int tiles, int K, bool f32, float alpha,         \
-                         float beta, int impl, hipStream_t st);
-TDG_DECL(nt)
-TDG_DECL(nn)
-TDG_DECL(tn)
-TDG_DECL(tt)
-#undef TDG_DECL
 
 // Column sum of a bf16 [M, N] matrix (row stride ld) into f32 out[N]
 // (out = beta*out + sum): the bias gradient. Deterministic two-stage:
@@ -170,7 +156,7 @@ extern "C" int tdg_gemm_grouped(const void* const* A, const void* const* B, void
 // problem is a run of its own). Returns 0 on success.
 extern "C" int tdg_gemm_ragged(const void* const* A, const void* const* B, void* const* C, int P,
                                const int* shapes, int K, int a_kc, int b_kc, int out_f32,
-                               float alpha, float beta, float* const* bias_out, int impl,
+                               float alpha, float beta, float* const* bias_out,
                                hipStream_t st) {
   if (P < 1 || P > R256_MAXP) return -2;
   R256Args args{};
@@ -202,10 +188,9 @@ extern "C" int tdg_gemm_ragged(const void* const* A, const void* const* B, void*
     if (args.bias_out[i] && a_kc) return -7;  // row sums need the MN-contiguous A path
   }
   args.ncls = ncls;
-  if (impl != 0 && (a_kc || b_kc)) return -4;  // (pipelined: TN weight gradients only)
-  if (a_kc && b_kc) return gemm_ragged_nt(args, tiles, K, out_f32 != 0, alpha, beta, 0, st);
-  if (a_kc && !b_kc) return out_f32 ? -4 : gemm_ragged_nn(args, tiles, K, false, alpha, beta, 0, st);
-  if (!a_kc && !b_kc) return gemm_ragged_tn(args, tiles, K, out_f32 != 0, alpha, beta, impl, st);
+  if (a_kc && b_kc) return gemm_ragged_nt(args, tiles, K, out_f32 != 0, alpha, beta, st);
+  if (a_kc && !b_kc) return out_f32 ? -4 : gemm_ragged_nn(args, tiles, K, false, alpha, beta, st);
+  if (!a_kc && !b_kc) return gemm_ragged_tn(args, tiles, K, out_f32 != 0, alpha, beta, st);
   return -4;
 }
 

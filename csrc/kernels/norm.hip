@@ -12,6 +12,7 @@
 // 219-248). One wave per row; each lane owns D/64 elements in runs of up to
 // 8 (tdg_ln.h RowMap: every access instruction is contiguous across the
 // wave), so D in {128, 256, 512, 1024}.
+#include "tdg_api.h"
 #include "tdg_common.h"
 #include "tdg_ln.h"
 #include "tdg_reduce.h"

@@ -8,14 +8,14 @@
 // of the step's issue points. Instead, a one-wave kernel captured INSIDE the
 // graph at the issue point bumps a device counter and publishes it to a
 // fine-grained (coherent) host word with a system-scope store; the comm
-// thread spins on that word (signal_wait in bindings.cpp, GIL released) and issues the
+// thread spins on that word (signal_wait in bindings/signal.cpp, GIL released) and issues the
 // collective once it reaches the value it expects. No graph boundary, no
 // event. Kernels of one stream run in order and each ends with a device-wide
 // release, so when the signal kernel runs every gradient before it is final
 // in memory; the store itself needs no release of its own (a release fence
 // would first write back this XCD's L2, and this kernel has nothing to
 // publish). A launch costs ~4.6 us of stream time (profiles/r6/dp_signal_issue.txt).
-#include <hip/hip_runtime.h>
+#include "tdg_api.h"
 
 #include <cstdint>
 

@@ -11,6 +11,7 @@
 //   dlogits = (softmax - onehot_smoothed) * scale   (scale = 1/(ntok*workers))
 // in place, or 0 for pad rows. Columns in [V, ldl) are zeroed so the padded
 // logits buffer can feed the dgrad / wgrad GEMMs directly.
+#include "tdg_api.h"
 #include "tdg_common.h"
 
 namespace tdg {

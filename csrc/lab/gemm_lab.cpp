@@ -13,6 +13,8 @@
 // workgroups' entry times) and the whole kernel span.
 #include "../kernels/gemm_impl.h"
 
+TDG_GEMM_LAYOUT(nt, true, true)  // the lab's cases are all NT: only that layout is compiled
+
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -96,10 +98,10 @@ int main(int argc, char** argv) {
     CK(hipMemcpy(A, hA.data(), hA.size() * 2, hipMemcpyHostToDevice));
     CK(hipMemcpy(B, hB.data(), hB.size() * 2, hipMemcpyHostToDevice));
     auto launch = [&]() {
-      const int rc = tdg_gemm(A, B, C, nullptr, nullptr, M, N, K, K, K, N, 0, 1, 1, 0, 0, 1.f, 0.f,
-                              c.cfg, 1, nullptr, st);
+      const int rc = tdg::gemm_nt(EPI_NONE, false, c.cfg, A, B, C, nullptr, nullptr, M, N, K, K, K,
+                                  N, 0, 1.f, 0.f, 1, nullptr, st);
       if (rc != 0) {
-        std::fprintf(stderr, "tdg_gemm rc %d\n", rc);
+        std::fprintf(stderr, "gemm_nt rc %d\n", rc);
         std::exit(1);
       }
     };

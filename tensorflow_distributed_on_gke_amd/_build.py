@@ -1,5 +1,5 @@
 """In-tree native build (no JIT cache, no hipify): generates a ninja file that
-compiles every HIP kernel for gfx950 with hipcc, the torch binding unit, and
+compiles every HIP kernel for gfx950 with hipcc, the torch binding units, and
 the pure-C++ host runtime, and links
 
   tensorflow_distributed_on_gke_amd/_C.so       (HIP kernels + torch bindings)
@@ -25,7 +25,7 @@ BUILD = ROOT / "build"
 ARCH = os.environ.get("TDG_OFFLOAD_ARCH", "gfx950")
 
 HIP_SOURCES = sorted((CSRC / "kernels").glob("*.hip"))
-BINDING = CSRC / "bindings.cpp"
+BINDINGS = sorted((CSRC / "bindings").glob("*.cpp"))
 NATIVE_SOURCES = sorted((CSRC / "runtime").glob("*.cpp"))
 
 
@@ -103,9 +103,10 @@ def write_ninja() -> Path:
         o = BUILD / (s.stem + ".hip.o")
         lines.append(f"build {o}: hip {s}")
         objs.append(str(o))
-    ob = BUILD / "bindings.o"
-    lines.append(f"build {ob}: bind {BINDING}")
-    objs.append(str(ob))
+    for s in BINDINGS:
+        o = BUILD / ("bind_" + s.stem + ".o")
+        lines.append(f"build {o}: bind {s}")
+        objs.append(str(o))
     ext = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
     lines.append(f"build {PKG / ('_C' + ext)}: link_hip {' '.join(objs)}")
     nobjs = []

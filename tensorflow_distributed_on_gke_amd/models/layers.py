@@ -416,9 +416,10 @@ def _proj_ln_fwd(a2, w: Param, b: Param, x, gamma: Param, beta: Param, site: int
     """GPU block tail y = LN(x + dropout(a2 @ w^T + b)) -> (y, saved): the
     output-projection GEMM (bias fused) then the fused dropout + residual +
     LayerNorm kernel. (GEMM + LayerNorm in one launch measured slower on
-    MI355X, both as full-row tiles -- every workgroup streams all of W,
-    csrc/lab/gemm_ln.hip -- and as 128-column tiles exchanging row partials
-    across workgroups: profiles/r5/ln_fused_ab.txt.)"""
+    MI355X, both as full-row tiles -- every workgroup streams all of W --
+    and as 128-column tiles exchanging row partials across workgroups; that
+    path is gone from the tree, its numbers are in
+    profiles/r5/ln_fused_ab.txt.)"""
     s = K.linear_fwd(a2, w.compute, b.master)
     return _ln_fwd(x, s.view(x.shape), gamma, beta, site, rt)
 
