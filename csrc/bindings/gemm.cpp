@@ -23,7 +23,8 @@ void check_group_c(const Tensor& C, bool f32, int64_t M, int64_t N, int64_t ldc)
 void gemm(const Tensor& A, const Tensor& B, const Tensor& C, const optional<Tensor>& bias,
           const optional<Tensor>& aux, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
           int64_t ldc, int64_t ldaux, bool a_kc, bool b_kc, int64_t epi, double alpha,
-          double beta, int64_t tile_cfg, int64_t splits, const optional<Tensor>& ws) {
+          double beta, int64_t tile_cfg, int64_t splits, const optional<Tensor>& ws,
+          const optional<Tensor>& relu_bits, int64_t ldbits) {
   TORCH_CHECK(C.is_cuda(), "C must be a GPU tensor");
   const bool f32 = C.scalar_type() == at::kFloat;
   TORCH_CHECK(f32 || C.scalar_type() == at::kBFloat16, "C must be f32 or bf16");
@@ -43,7 +44,19 @@ void gemm(const Tensor& A, const Tensor& B, const Tensor& C, const optional<Tens
     bptr = bias->data_ptr<float>();
   }
   const void* xptr = nullptr;
-  if (epi == 3) {
+  // ReLU mask as a bitmap [M][ldbits] (uint8, bit e of byte c = column 8c + e):
+  // written by the bias+ReLU epilogue, read by the ReLU-backward one instead of aux
+  void* bits = nullptr;
+  if (relu_bits.has_value()) {
+    TORCH_CHECK(epi == 2 || epi == 3, "gemm: relu_bits needs the bias+ReLU or ReLU-backward epilogue");
+    TORCH_CHECK(relu_bits->is_cuda() && relu_bits->scalar_type() == at::kByte,
+                "relu_bits must be a uint8 GPU tensor");
+    TORCH_CHECK(N % 8 == 0, "gemm: relu_bits needs N % 8 == 0");
+    TORCH_CHECK(ldbits >= N / 8, "gemm: ldbits < N / 8");
+    check_extent(*relu_bits, M, ldbits, N / 8, "relu_bits");
+    bits = relu_bits->data_ptr();
+  }
+  if (epi == 3 && bits == nullptr) {
     TORCH_CHECK(aux.has_value(), "gemm: DRELU epilogue needs aux");
     check_bf16(*aux, "aux");
     check_extent(*aux, M, ldaux, N, "aux");
@@ -60,7 +73,7 @@ void gemm(const Tensor& A, const Tensor& B, const Tensor& C, const optional<Tens
   const int rc = tdg_gemm(A.data_ptr(), B.data_ptr(), C.data_ptr(), bptr, xptr, (int)M, (int)N,
                           (int)K, (int)lda, (int)ldb, (int)ldc, (int)ldaux, a_kc, b_kc, (int)epi,
                           f32, (float)alpha, (float)beta, (int)tile_cfg, (int)splits, wptr,
-                          stream_of(A));
+                          stream_of(A), bits, (int)ldbits);
   check_err(rc, "tdg gemm");
 }
 
@@ -180,7 +193,11 @@ void colsum_grouped(const std::vector<Tensor>& Xs, const std::vector<Tensor>& ou
 }  // namespace
 
 void def_gemm(py::module_& m) {
-  m.def("gemm", &gemm);
+  m.def("gemm", &gemm, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("bias"), py::arg("aux"),
+        py::arg("M"), py::arg("N"), py::arg("K"), py::arg("lda"), py::arg("ldb"), py::arg("ldc"),
+        py::arg("ldaux"), py::arg("a_kc"), py::arg("b_kc"), py::arg("epi"), py::arg("alpha"),
+        py::arg("beta"), py::arg("tile_cfg"), py::arg("splits"), py::arg("ws"),
+        py::arg("relu_bits") = optional<Tensor>(), py::arg("ldbits") = 0);
   m.def("gemm_grouped", &gemm_grouped);
   m.def("gemm_ragged", &gemm_ragged, py::arg("As"), py::arg("Bs"), py::arg("Cs"), py::arg("shapes"),
         py::arg("K"), py::arg("a_kc"), py::arg("b_kc"), py::arg("alpha"), py::arg("beta"),

@@ -14,11 +14,15 @@
 extern "C" {
 
 // ---------------------------------------------------------------- gemm.hip
-// a_kc / b_kc: operand is K-contiguous; epi: tdg::Epi; ws: split-K slabs
+// a_kc / b_kc: operand is K-contiguous; epi: tdg::Epi (0..3); ws: split-K slabs.
+// relu_bits (or null): the ReLU mask as a bitmap [M][ldbits] bytes, bit e of
+// byte c = column 8c + e -- written by epi 2 (bits = output > 0), read by
+// epi 3 instead of aux. Needs N % 8 == 0, ldc % 8 == 0, a 16-byte aligned
+// bf16 C and no split-K (-11 / -12 otherwise).
 int tdg_gemm(const void* A, const void* B, void* C, const float* bias, const void* aux, int M,
              int N, int K, int lda, int ldb, int ldc, int ldaux, int a_kc, int b_kc, int epi,
              int out_f32, float alpha, float beta, int tile_cfg, int splits, float* ws,
-             hipStream_t st);
+             hipStream_t st, void* relu_bits, int ldbits);
 int tdg_gemm_grouped(const void* const* A, const void* const* B, void* const* C, int G, int M,
                      int N, int K, int lda, int ldb, int ldc, int a_kc, int b_kc, int out_f32,
                      float alpha, float beta, int tile_cfg, hipStream_t st);

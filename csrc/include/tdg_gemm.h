@@ -202,13 +202,24 @@ enum Epi : int {
   EPI_BIAS = 1,       // alpha*acc + bias[n]
   EPI_BIAS_RELU = 2,  // relu(alpha*acc + bias[n])
   EPI_DRELU = 3,      // alpha*acc * (aux[m,n] > 0)      (ReLU backward fused in dgrad)
+  // The same two with the ReLU mask as a bitmap (bf16 out only): one byte per
+  // 8 columns, bits[m][c] bit e = column 8c + e (numpy.packbits, bitorder
+  // "little"). The kernels take the bitmap through their aux / ldaux
+  // parameters (row stride in bytes). The launcher (tdg_gemm) guarantees
+  // N % 8 == 0, ldc % 8 == 0 and a 16-byte aligned C, so every in-range
+  // 16-byte output chunk is whole and takes the vector path.
+  EPI_BIAS_RELU_BITS = 4,  // EPI_BIAS_RELU, and writes bits = (stored bf16 > 0)
+  EPI_DRELU_BITS = 5,      // EPI_DRELU with the mask read from bits
 };
+constexpr bool epi_has_bias(int e) { return e == EPI_BIAS || e == EPI_BIAS_RELU || e == EPI_BIAS_RELU_BITS; }
+constexpr bool epi_has_relu(int e) { return e == EPI_BIAS_RELU || e == EPI_BIAS_RELU_BITS; }
+constexpr bool epi_has_bits(int e) { return e == EPI_BIAS_RELU_BITS || e == EPI_DRELU_BITS; }
 
 // 4 bias values of columns n..n+3 (clamped to N-1 past the edge).
 template <int EPI>
 __device__ __forceinline__ f32x4 load_bias4(const float* __restrict__ bias, int n, int N) {
   f32x4 b = {0.f, 0.f, 0.f, 0.f};
-  if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU) {
+  if constexpr (epi_has_bias(EPI)) {
     if (n + 4 <= N && (reinterpret_cast<uintptr_t>(bias + n) & 15) == 0) {
       b = *reinterpret_cast<const f32x4*>(bias + n);
     } else {
@@ -308,6 +319,49 @@ struct EpiLds {
   static constexpr int BYTES = RPASS * SP;       // image bytes per wave
   static_assert(RPASS % 16 == 0 && (TM * 16) % RPASS == 0, "passes of whole 16-row sub-tiles");
   static_assert((RPASS * CPR) % 64 == 0, "whole chunk iterations");
+  // ReLU bitmap (EPI_*_BITS): a row of the wave tile is CPR mask bytes (one
+  // per 16-byte output chunk). Lane l holds the bytes of tile rows l, l + 64,
+  // ... in MBW dwords each (mask_load, issued before the main loop). Inside a
+  // pass the bytes travel through the 16 pad bytes of the image rows: the
+  // consumer's holders write their row's CPR bytes there and every chunk
+  // reads its own; the producer's chunks write theirs and lane l stores row
+  // l's CPR bytes with one 4- or 8-byte store per pass.
+  static constexpr bool BITS = epi_has_bits(EPI);
+  static constexpr int PAD = TN * 16 * ES;                       // pad offset in an image row
+  static constexpr int MBW = CPR / 4 > 0 ? CPR / 4 : 1;          // dwords per held row
+  static constexpr int MBR = MBW * ((TM * 16 + 63) / 64);        // mask registers per lane
+  static_assert(!BITS || (!OUT_F32 && (CPR == 4 || CPR == 8) && (RPASS == 64 || RPASS == TM * 16)),
+                "bitmap epilogues: bf16 out, 32/64-wide wave tiles, rows of a pass held by lanes 0..RPASS-1");
+
+  // The wave tile's mask bytes (consumer prologue). bits: bitmap, ldb its row
+  // stride in bytes. Rows past M are clamped; a tile hanging over N (or an
+  // unaligned bitmap) loads byte by byte, only the bytes that exist.
+  __device__ static __forceinline__ void mask_load(uint32_t (&mb)[MBR], const unsigned char* bits,
+                                                   int ldb, int M, int N, int mw0, int nw0, int lane) {
+    const bool wide = nw0 + TN * 16 <= N && (ldb % (4 * MBW)) == 0 &&
+                      (reinterpret_cast<uintptr_t>(bits) % (4 * MBW)) == 0;
+#pragma unroll
+    for (int k = 0; k < MBR / MBW; ++k) {
+      int m = mw0 + lane + 64 * k;
+      m = m < M ? m : M - 1;
+      const unsigned char* p = bits + (size_t)m * ldb + (nw0 >> 3);
+      if (wide) {
+        if constexpr (MBW == 2) {
+          const uint2 v = *reinterpret_cast<const uint2*>(p);
+          mb[2 * k] = v.x;
+          mb[2 * k + 1] = v.y;
+        } else {
+          mb[k] = *reinterpret_cast<const uint32_t*>(p);
+        }
+      } else {
+#pragma unroll
+        for (int w = 0; w < MBW; ++w) mb[MBW * k + w] = 0u;
+#pragma unroll
+        for (int c = 0; c < CPR; ++c)
+          if (nw0 + 8 * c < N) mb[MBW * k + c / 4] |= (uint32_t)p[c] << (8 * (c % 4));
+      }
+    }
+  }
 
   // m_of / n_of: row / column of chunk iteration t (pass 0) -- for prefetch.
   __device__ static __forceinline__ int row_of(int lane, int t) { return (lane + 64 * t) / CPR; }
@@ -319,8 +373,20 @@ struct EpiLds {
                                              const float* __restrict__ bias,
                                              const bf16_t* __restrict__ aux, int ldaux, bool vec) {
     int4 none[ITER];
+    uint32_t nomask[MBR];
     run_pre<false>(wimg, acc, lane, Cv, ldc, M, N, mw0, nw0, alpha, beta, bias, aux, ldaux, vec,
-                   none, false, none, false);
+                   none, false, none, false, nomask);
+  }
+  // EPI_DRELU_BITS: mb from mask_load
+  __device__ static __forceinline__ void run_mask(char* wimg, const f32x4 (&acc)[TM][TN], int lane,
+                                                  void* __restrict__ Cv, int ldc, int M, int N,
+                                                  int mw0, int nw0, float alpha, float beta,
+                                                  const float* __restrict__ bias,
+                                                  const bf16_t* __restrict__ aux, int ldaux, bool vec,
+                                                  const uint32_t (&mb)[MBR]) {
+    int4 none[ITER];
+    run_pre<false>(wimg, acc, lane, Cv, ldc, M, N, mw0, nw0, alpha, beta, bias, aux, ldaux, vec,
+                   none, false, none, false, mb);
   }
   // With operands prefetched in the chunk layout (arrays indexed by constants
   // only after unrolling: no private-memory copies).
@@ -331,7 +397,8 @@ struct EpiLds {
                                                  const float* __restrict__ bias,
                                                  const bf16_t* __restrict__ aux, int ldaux, bool vec,
                                                  const int4 (&pre_aux)[ITER], bool use_aux,
-                                                 const int4 (&pre_c)[ITER], bool use_c) {
+                                                 const int4 (&pre_c)[ITER], bool use_c,
+                                                 const uint32_t (&mb)[MBR]) {
     const int g = lane >> 4, r16 = lane & 15;
     // 16-byte chunk path: C rows 16-byte aligned, the ReLU mask likewise
     bool vok = vec && ((ldc * ES) % 16) == 0 && (reinterpret_cast<uintptr_t>(Cv) & 15) == 0;
@@ -374,6 +441,15 @@ struct EpiLds {
           }
         }
       }
+      if constexpr (EPI == EPI_DRELU_BITS) {
+        // this pass's mask bytes -> the pad of their image rows
+        if (RPASS == 64 || lane < RPASS) {
+          const int k = p * RPASS / 64;  // (a constant once the pass loop is unrolled)
+          char* dst = wimg + lane * SP + PAD;
+          if constexpr (MBW == 2) *reinterpret_cast<uint2*>(dst) = uint2{mb[2 * k], mb[2 * k + 1]};
+          else *reinterpret_cast<uint32_t*>(dst) = mb[k];
+        }
+      }
       // 1) accumulators (alpha, bias, relu applied) -> image
 #pragma unroll
       for (int ii = 0; ii < RPASS / 16; ++ii) {
@@ -385,7 +461,7 @@ struct EpiLds {
           for (int r = 0; r < 4; ++r) {
             v[r] = alpha * acc[i][j][r];
             if constexpr (EPI == EPI_BIAS) v[r] += bn[j][r];
-            if constexpr (EPI == EPI_BIAS_RELU) v[r] = fmaxf(v[r] + bn[j][r], 0.f);
+            if constexpr (epi_has_relu(EPI)) v[r] = fmaxf(v[r] + bn[j][r], 0.f);
           }
           char* dst = wimg + (16 * ii + r16) * SP + (16 * j + 4 * g) * ES;
           if constexpr (OUT_F32) {
@@ -411,7 +487,19 @@ struct EpiLds {
         VecT vals = *reinterpret_cast<const VecT*>(wimg + row * SP + ch * 16);
         if (m >= M || n >= N) continue;
         char* cp = reinterpret_cast<char*>(Cv) + ((size_t)m * ldc + n) * ES;
-        if (vok && n + EPC <= N) {
+        if (BITS || (vok && n + EPC <= N)) {  // (BITS: whole aligned chunks, see Epi)
+          if constexpr (EPI == EPI_DRELU_BITS) {
+            const uint32_t b = *reinterpret_cast<const unsigned char*>(wimg + row * SP + PAD + ch);
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+              if (!((b >> e) & 1u)) vals[e] = 0;
+          }
+          if constexpr (EPI == EPI_BIAS_RELU_BITS) {
+            uint32_t b = 0;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) b |= (bf2f((bf16_t)vals[e]) > 0.f ? 1u : 0u) << e;
+            *reinterpret_cast<unsigned char*>(wimg + row * SP + PAD + ch) = (unsigned char)b;
+          }
           if constexpr (EPI == EPI_DRELU) {
             if constexpr (EPC == 8) {
               // vok: either the caller prefetched the mask or la[] holds it
@@ -443,7 +531,7 @@ struct EpiLds {
 #else
           *reinterpret_cast<VecT*>(cp) = vals;
 #endif
-        } else {
+        } else if constexpr (!BITS) {
 #pragma unroll
           for (int e = 0; e < EPC; ++e) {
             if (n + e >= N) break;
@@ -460,6 +548,26 @@ struct EpiLds {
               if (beta != 0.f) v += beta * bf2f(*c);
               *c = f2bf(v);
             }
+          }
+        }
+      }
+      if constexpr (EPI == EPI_BIAS_RELU_BITS) {
+        // row `lane` of the pass: its CPR mask bytes leave as one store
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every chunk's byte is in the pad
+        unsigned char* bits = reinterpret_cast<unsigned char*>(const_cast<bf16_t*>(aux));
+        const int m = mw0 + p * RPASS + lane;
+        if ((RPASS == 64 || lane < RPASS) && m < M && nw0 < N) {
+          const char* src = wimg + lane * SP + PAD;
+          unsigned char* dst = bits + (size_t)m * ldaux + (nw0 >> 3);
+          const bool wide = nw0 + TN * 16 <= N && (ldaux % (4 * MBW)) == 0 &&
+                            (reinterpret_cast<uintptr_t>(bits) % (4 * MBW)) == 0;
+          if (wide) {
+            if constexpr (MBW == 2) *reinterpret_cast<uint2*>(dst) = *reinterpret_cast<const uint2*>(src);
+            else *reinterpret_cast<uint32_t*>(dst) = *reinterpret_cast<const uint32_t*>(src);
+          } else {
+#pragma unroll
+            for (int c = 0; c < CPR; ++c)
+              if (nw0 + 8 * c < N) dst[c] = (unsigned char)src[c];
           }
         }
       }

@@ -123,10 +123,23 @@ __global__ __launch_bounds__(256) void reduce_partials_grouped_kernel(ColsumGrou
 extern "C" int tdg_gemm(const void* A, const void* B, void* C, const float* bias, const void* aux,
                         int M, int N, int K, int lda, int ldb, int ldc, int ldaux, int a_kc,
                         int b_kc, int epi, int out_f32, float alpha, float beta, int tile_cfg,
-                        int splits, float* ws, hipStream_t st) {
+                        int splits, float* ws, hipStream_t st, void* relu_bits, int ldbits) {
   const bf16_t* a = (const bf16_t*)A;
   const bf16_t* b = (const bf16_t*)B;
   const bf16_t* x = (const bf16_t*)aux;
+  if (relu_bits) {
+    // ReLU mask as a bitmap: the *_BITS epilogues, which take the bitmap and
+    // its row stride (bytes) in place of aux / ldaux (tdg_gemm.h)
+    if (epi != EPI_BIAS_RELU && epi != EPI_DRELU) return -11;
+    if (out_f32 || N % 8 != 0 || ldc % 8 != 0 || (reinterpret_cast<uintptr_t>(C) & 15) != 0 ||
+        ldbits < N / 8)
+      return -11;
+    epi = epi == EPI_BIAS_RELU ? EPI_BIAS_RELU_BITS : EPI_DRELU_BITS;
+    x = (const bf16_t*)relu_bits;
+    ldaux = ldbits;
+  } else if (epi > EPI_DRELU) {
+    return -1;
+  }
   auto fn = a_kc ? (b_kc ? gemm_nt : gemm_nn) : (b_kc ? gemm_tt : gemm_tn);
   return fn(epi, out_f32 != 0, tile_cfg, a, b, C, bias, x, M, N, K, lda, ldb, ldc, ldaux, alpha,
             beta, splits, ws, st);

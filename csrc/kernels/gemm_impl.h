@@ -131,6 +131,12 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(
     if (pre_c && in)
       c_r[t] = *reinterpret_cast<const int4*>(reinterpret_cast<const OutT*>(Cv) + (size_t)m * ldc + n);
   }
+  // EPI_DRELU_BITS: the wave tile's ReLU mask as bits (aux = the bitmap), one
+  // or two dwords per lane, likewise older than every DMA
+  uint32_t mask_r[Epi::MBR];
+  if constexpr (EPI == EPI_DRELU_BITS)
+    Epi::mask_load(mask_r, reinterpret_cast<const unsigned char*>(aux), ldaux, M, N, m0 + wm * WTM,
+                   n0 + wn * WTN, lane);
 
   f32x4 acc[TM][TN];
 #pragma unroll
@@ -252,7 +258,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(
               nullptr, 0, epi_vec_ok<EPI_NONE, true>(Cs, ldc, nullptr, 0));
   } else {
     Epi::template run_pre<true>(smem + wid * Epi::BYTES, acc, lane, Cv, ldc, M, N, mw0, nw0, alpha,
-                                beta, bias, aux, ldaux, vec, aux_r, pre_aux, c_r, pre_c);
+                                beta, bias, aux, ldaux, vec, aux_r, pre_aux, c_r, pre_c, mask_r);
   }
 #ifdef TDG_STAMPS
   TDG_STAMP(3);
@@ -458,6 +464,16 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const R256Args args,
     if (ph == 0) bsum0 = bs;
     else bsum1 = bs;
   };
+  // EPI_DRELU_BITS: the wave tile's ReLU mask as bits (aux = the bitmap),
+  // 128 rows x 8 bytes = 4 VGPRs per lane, loaded here -- older than every
+  // LDS-DMA, so the counted waits below also cover it -- and in registers when
+  // the epilogue starts. (The bf16 mask of EPI_DRELU would be 64 VGPRs per
+  // lane: it is loaded per epilogue pass, with the MFMAs idle.)
+  using Epi = EpiLds<EPI, OUT_F32, 8, 4, (OUT_F32 ? 32 : 64)>;
+  uint32_t mask_r[Epi::MBR];
+  if constexpr (EPI == EPI_DRELU_BITS)
+    Epi::mask_load(mask_r, reinterpret_cast<const unsigned char*>(aux), ldaux, M, N, m0 + wm * 128,
+                   n0 + wn * 64, lane);
   {
 #pragma unroll
     for (int h = 0; h < 4; ++h) issue_half(0, h);
@@ -606,11 +622,14 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const R256Args args,
   wait_vmcnt<0>();
   lds_barrier();
   {
-    constexpr int RPASS = OUT_F32 ? 32 : 64;
-    using Epi = EpiLds<EPI, OUT_F32, 8, 4, RPASS>;
     static_assert(8 * Epi::BYTES <= 2 * 4 * 128 * BK * 2, "epilogue images fit in the stages");
-    Epi::run(smem + wid * Epi::BYTES, acc, lane, Cv, ldc, M, N, m0 + wm * 128, n0 + wn * 64, alpha,
-             beta, bias, aux, ldaux, epi_vec_ok<EPI, OUT_F32>(Cv, ldc, aux, ldaux));
+    if constexpr (EPI == EPI_DRELU_BITS)
+      Epi::run_mask(smem + wid * Epi::BYTES, acc, lane, Cv, ldc, M, N, m0 + wm * 128, n0 + wn * 64,
+                    alpha, beta, bias, aux, ldaux, epi_vec_ok<EPI, OUT_F32>(Cv, ldc, aux, ldaux),
+                    mask_r);
+    else
+      Epi::run(smem + wid * Epi::BYTES, acc, lane, Cv, ldc, M, N, m0 + wm * 128, n0 + wn * 64, alpha,
+               beta, bias, aux, ldaux, epi_vec_ok<EPI, OUT_F32>(Cv, ldc, aux, ldaux));
   }
 #ifdef TDG_STAMPS
   TDG_STAMP(3);
@@ -698,7 +717,7 @@ void launch_cfg(const bf16_t* A, const bf16_t* B, void* C, const float* bias, co
 template <bool AK, bool BKc, int EPI, bool F32>
 constexpr bool has_256() {
   if (AK && BKc) return !F32 || EPI == EPI_NONE;
-  if (AK && !BKc) return !F32 && (EPI == EPI_NONE || EPI == EPI_DRELU);
+  if (AK && !BKc) return !F32 && (EPI == EPI_NONE || EPI == EPI_DRELU || EPI == EPI_DRELU_BITS);
   if (!AK && !BKc) return EPI == EPI_NONE;
   return false;
 }
@@ -758,6 +777,9 @@ template <int BM, int BN, int WM, int WN, int NS, bool AK, bool BKc, int EPI, bo
 bool launch_pipe(const bf16_t* A, const bf16_t* B, void* C, const float* bias, const bf16_t* aux,
                  int M, int N, int K, int lda, int ldb, int ldc, int ldaux, float alpha, float beta,
                  hipStream_t st) {
+  // (bitmap epilogues: wave tiles up to 64 columns, EpiLds)
+  if constexpr (epi_has_bits(EPI) && BN / WN > 64) return false;
+  else {
   if (K % PK != 0 || K <= 0) return false;
   const long long ab = AK ? (long long)(M - 1) * lda + K : (long long)(K - 1) * lda + M;
   const long long bb = BKc ? (long long)(N - 1) * ldb + K : (long long)(K - 1) * ldb + N;
@@ -776,6 +798,7 @@ bool launch_pipe(const bf16_t* A, const bf16_t* B, void* C, const float* bias, c
                      st, A, B, C, bias, aux, M, N, K, lda, ldb, ldc, ldaux, alpha, beta,
                      (int)(ab * 2), (int)(bb * 2));
   return true;
+  }
 }
 
 template <bool AK, bool BKc, int EPI, bool F32>
@@ -872,6 +895,16 @@ int dispatch_epi(int epi, bool f32, int tile_cfg, const bf16_t* A, const bf16_t*
   TDG_E(EPI_BIAS, true)
   TDG_E(EPI_BIAS_RELU, false)
   TDG_E(EPI_DRELU, false)
+  // ReLU mask as a bitmap: the forward layout writes it, both dgrad layouts
+  // read it. No split-K (the reduction kernel has no bitmap path), and not the
+  // one-wave-per-SIMD pipelined tiles (128-column wave tiles).
+  if (epi_has_bits(epi) && (splits > 1 || (tile_cfg >= 23 && tile_cfg <= 26))) return -12;
+  if constexpr (AK && BKc) {
+    TDG_E(EPI_BIAS_RELU_BITS, false)
+  }
+  if constexpr (AK) {
+    TDG_E(EPI_DRELU_BITS, false)
+  }
 #undef TDG_E
   return -1;
 }

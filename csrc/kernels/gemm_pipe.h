@@ -316,6 +316,15 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_pipe_kernel(
     for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int abase = wm * WTM, bbase = wn * WTN;
+  // EPI_DRELU_BITS: the wave tile's ReLU mask as bits (aux = the bitmap),
+  // loaded before the first LDS-DMA (older than all of them: the counted
+  // waits stay exact) and in registers when the epilogue starts
+  constexpr int RPASS = OUT_F32 ? (WTM < 32 ? WTM : 32) : (WTM > 64 ? 64 : WTM);
+  using Epi = EpiLds<EPI, OUT_F32, TM, TN, RPASS>;
+  uint32_t mask_r[Epi::MBR];
+  if constexpr (EPI == EPI_DRELU_BITS)
+    Epi::mask_load(mask_r, reinterpret_cast<const unsigned char*>(aux), ldaux, M, N, m0 + abase,
+                   n0 + bbase, lane);
   // prologue: NS-1 tiles in flight, tile 0 landed, its fragments requested
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s)
@@ -359,11 +368,14 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_pipe_kernel(
   {
     using OutT = typename std::conditional<OUT_F32, float, bf16_t>::type;
     (void)sizeof(OutT);
-    constexpr int RPASS = OUT_F32 ? (WTM < 32 ? WTM : 32) : (WTM > 64 ? 64 : WTM);
-    using Epi = EpiLds<EPI, OUT_F32, TM, TN, RPASS>;
     static_assert(NW * Epi::BYTES <= NS * SB, "epilogue images fit in the stages");
-    Epi::run(smem + wid * Epi::BYTES, acc, lane, Cv, ldc, M, N, m0 + wm * WTM, n0 + wn * WTN, alpha,
-             beta, bias, aux, ldaux, epi_vec_ok<EPI, OUT_F32>(Cv, ldc, aux, ldaux));
+    if constexpr (EPI == EPI_DRELU_BITS)
+      Epi::run_mask(smem + wid * Epi::BYTES, acc, lane, Cv, ldc, M, N, m0 + wm * WTM, n0 + wn * WTN,
+                    alpha, beta, bias, aux, ldaux, epi_vec_ok<EPI, OUT_F32>(Cv, ldc, aux, ldaux),
+                    mask_r);
+    else
+      Epi::run(smem + wid * Epi::BYTES, acc, lane, Cv, ldc, M, N, m0 + wm * WTM, n0 + wn * WTN, alpha,
+               beta, bias, aux, ldaux, epi_vec_ok<EPI, OUT_F32>(Cv, ldc, aux, ldaux));
   }
 }
 

@@ -1055,6 +1055,12 @@ class CrossAttnBlockFn(torch.autograd.Function):
 
 
 # =============================================================================== feed-forward block
+# the bf16 training forward's FFN1 GEMM also writes its ReLU mask as a bitmap
+# (1 bit per hidden element); the ReLU-backward dgrad reads that, prefetched
+# before its main loop, instead of the bf16 hidden activation (0: the bf16 mask)
+RELU_BITS = os.environ.get("TDG_RELU_BITS", "1") != "0"
+
+
 class FFNBlockFn(torch.autograd.Function):
     """y = LN(x + dropout(Dense(d)(Dense(ff, relu)(x))))."""
 
@@ -1067,6 +1073,7 @@ class FFNBlockFn(torch.autograd.Function):
         ctx.meta = (site, rt)
         ctx.f8 = None
         ctx.lean = False
+        ctx.hbits = None
         if x.is_cuda and rt.fp8 is not None:
             st = rt.fp8
             xs, hs = st.ffn_slots[id(w1)]
@@ -1088,7 +1095,12 @@ class FFNBlockFn(torch.autograd.Function):
             ctx.f8 = (x8, h8) if rt.training else None
             ctx.lean = lean
         elif x.is_cuda:
-            h = K.linear_fwd(x2, w1.compute, b1.master, relu=True)
+            ff = w1.shape[0]
+            hbits = None
+            if RELU_BITS and rt.training and ff % 8 == 0:
+                hbits = torch.empty(B * L, ff // 8, dtype=torch.uint8, device=x.device)
+            h = K.linear_fwd(x2, w1.compute, b1.master, relu=True, relu_bits=hbits)
+            ctx.hbits = hbits
             f = None  # second projection fused with the LayerNorm below
         else:
             h = torch.relu(x2 @ w1.master.t() + b1.master)
@@ -1154,12 +1166,15 @@ class FFNBlockFn(torch.autograd.Function):
                 fp8.gemm_bf8_dgrad(dpre8, st.gmeta, gh, w1t8, st.meta, s1t, dh.view(M, d), beta=1.0,
                                    w_plain=wp)
                 return (dh.view(B, L, d),) + (None,) * 8
+            # ReLU mask: the forward's bitmap if it wrote one (h is still saved:
+            # the W2 weight gradient reads it)
+            mask = dict(relu_bits=ctx.hbits) if ctx.hbits is not None else dict(relu_aux=h)
             if w2.compute_t is not None and not w2.compute_t_stale:
                 # NT layout against W2^T (ParamStore.add_transposed; stale while
                 # an fp8 backward had the re-transposes paused: NN below)
-                dpre = K.linear_dgrad_t(ds2, w2.compute_t, relu_aux=h)
+                dpre = K.linear_dgrad_t(ds2, w2.compute_t, **mask)
             else:
-                dpre = K.linear_dgrad(ds2, w2.compute, d, relu_aux=h)
+                dpre = K.linear_dgrad(ds2, w2.compute, d, **mask)
             _wgrad(rt, dpre, x2, ff, w1, b1)
             dx = _dgrad_res(dpre, w1, ff, dh)
             return (dx.view(B, L, d),) + (None,) * 8

@@ -162,15 +162,25 @@ def _tok_bucket(v: int) -> int:
 
 
 def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc, b_kc, epi=EPI_NONE, bias=None, aux=None,
-         ldaux=0, alpha=1.0, beta=0.0, cfg: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+         ldaux=0, alpha=1.0, beta=0.0, cfg: Optional[Tuple[int, int]] = None,
+         relu_bits: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Every GEMM of the model: the in-tree MFMA kernels (csrc/kernels/gemm.hip)
-    with the tile config from the tuned table, else the heuristic."""
+    with the tile config from the tuned table, else the heuristic.
+
+    relu_bits: the ReLU mask as a uint8 bitmap [M, >= N / 8] (bit e of byte c =
+    column 8c + e, i.e. numpy.packbits(h > 0, axis=1, bitorder="little")):
+    EPI_BIAS_RELU writes it, EPI_DRELU reads it instead of aux. N % 8 == 0;
+    the tuning key is that of the plain epilogue."""
 
     def run(c, out=Cout):
         tile, splits = c
         ws = workspace("splitk", splits * M * ldc, A.device) if splits > 1 else None
-        C().gemm(A, B, out, bias, aux, M, N, K, lda, ldb, ldc, ldaux, a_kc, b_kc, epi, alpha,
-                 beta, tile, splits, ws)
+        if relu_bits is None:
+            C().gemm(A, B, out, bias, aux, M, N, K, lda, ldb, ldc, ldaux, a_kc, b_kc, epi, alpha,
+                     beta, tile, splits, ws)
+        else:
+            C().gemm(A, B, out, bias, aux, M, N, K, lda, ldb, ldc, ldaux, a_kc, b_kc, epi, alpha,
+                     beta, tile, splits, ws, relu_bits=relu_bits, ldbits=relu_bits.stride(0))
 
     if cfg is None:
         # token-count dimensions (M of forward / dgrad, K of wgrad) are bucketed
@@ -206,28 +216,46 @@ def tuned_table() -> Dict[str, str]:
             for k, v in _TUNED.items()}
 
 
+def pack_relu_bits(h: torch.Tensor) -> torch.Tensor:
+    """The ReLU bitmap [M, N / 8] of a hidden activation h [M, N] (N % 8 == 0),
+    as the bias+ReLU epilogue writes it: bit e of byte c = (h[:, 8c + e] > 0)."""
+    M, N = h.shape
+    w = (1 << torch.arange(8, device=h.device, dtype=torch.int32))
+    return ((h > 0).view(M, N // 8, 8).to(torch.int32) * w).sum(-1).to(torch.uint8)
+
+
 def linear_fwd(x2: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], relu: bool = False,
-               out: Optional[torch.Tensor] = None, ldc: Optional[int] = None) -> torch.Tensor:
-    """y[M,N] = x[M,K] @ w[N,K]^T + bias (bf16 out)."""
+               out: Optional[torch.Tensor] = None, ldc: Optional[int] = None,
+               relu_bits: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[M,N] = x[M,K] @ w[N,K]^T + bias (bf16 out). relu_bits (with relu):
+    also writes the ReLU bitmap (y > 0) into this uint8 [M, >= N / 8] tensor."""
     M, K = x2.shape
     N = w.shape[0]
     ldc = ldc or N
     if out is None:
         out = torch.empty(M, ldc, dtype=torch.bfloat16, device=x2.device)
     epi = EPI_BIAS_RELU if relu else (EPI_BIAS if bias is not None else EPI_NONE)
-    return gemm(x2, w, out, M, N, K, x2.stride(0), w.stride(0), ldc, True, True, epi, bias=bias)
+    if relu_bits is not None and not relu:
+        raise ValueError("linear_fwd: relu_bits needs relu=True")
+    return gemm(x2, w, out, M, N, K, x2.stride(0), w.stride(0), ldc, True, True, epi, bias=bias,
+                relu_bits=relu_bits)
 
 
 def linear_dgrad(dy2: torch.Tensor, w: torch.Tensor, N: int, relu_aux: Optional[torch.Tensor] = None,
-                 out: Optional[torch.Tensor] = None, beta: float = 0.0) -> torch.Tensor:
-    """dx[M,K] = dy[M,N] @ w[N,K] (optionally * (relu_aux > 0))."""
+                 out: Optional[torch.Tensor] = None, beta: float = 0.0,
+                 relu_bits: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dx[M,K] = dy[M,N] @ w[N,K] (optionally * (relu_aux > 0), the mask given
+    as the bf16 activation relu_aux or as its bitmap relu_bits)."""
     M = dy2.shape[0]
     K = w.shape[1]
     if out is None:
         out = torch.empty(M, K, dtype=torch.bfloat16, device=dy2.device)
-    epi = EPI_DRELU if relu_aux is not None else EPI_NONE
+    if relu_bits is not None:
+        relu_aux = None
+    epi = EPI_DRELU if (relu_aux is not None or relu_bits is not None) else EPI_NONE
     return gemm(dy2, w, out, M, K, N, dy2.stride(0), w.stride(0), out.stride(0), True, False, epi,
-                aux=relu_aux, ldaux=(relu_aux.stride(0) if relu_aux is not None else 0), beta=beta)
+                aux=relu_aux, ldaux=(relu_aux.stride(0) if relu_aux is not None else 0), beta=beta,
+                relu_bits=relu_bits)
 
 
 def transpose_grouped(srcs, dsts) -> None:
@@ -237,7 +265,8 @@ def transpose_grouped(srcs, dsts) -> None:
 
 
 def linear_dgrad_t(dy2: torch.Tensor, w_t: torch.Tensor, relu_aux: Optional[torch.Tensor] = None,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None,
+                   relu_bits: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dx[M,N] = dy[M,K] @ w[K,N] computed against the weight's transposed copy
     w_t [N, K] (K-contiguous): the forward (NT) operand layout, whose kernels
     are faster than the N-contiguous dgrad ones; optional ReLU-backward mask."""
@@ -245,9 +274,12 @@ def linear_dgrad_t(dy2: torch.Tensor, w_t: torch.Tensor, relu_aux: Optional[torc
     N = w_t.shape[0]
     if out is None:
         out = torch.empty(M, N, dtype=torch.bfloat16, device=dy2.device)
-    epi = EPI_DRELU if relu_aux is not None else EPI_NONE
+    if relu_bits is not None:
+        relu_aux = None
+    epi = EPI_DRELU if (relu_aux is not None or relu_bits is not None) else EPI_NONE
     return gemm(dy2, w_t, out, M, N, K, dy2.stride(0), w_t.stride(0), out.stride(0), True, True, epi,
-                aux=relu_aux, ldaux=(relu_aux.stride(0) if relu_aux is not None else 0))
+                aux=relu_aux, ldaux=(relu_aux.stride(0) if relu_aux is not None else 0),
+                relu_bits=relu_bits)
 
 
 def linear_wgrad(dy2: torch.Tensor, x2: torch.Tensor, N: int, dw: torch.Tensor,
