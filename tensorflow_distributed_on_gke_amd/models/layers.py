@@ -34,19 +34,19 @@ from __future__ import annotations
 
 import math
 import os
-from dataclasses import dataclass, field
+from collections import namedtuple
+from dataclasses import dataclass
 from typing import Optional
 
 import torch
 
 from tensorflow_distributed_on_gke_amd.models.params import Param, ParamStore
+from tensorflow_distributed_on_gke_amd.models.wgrad import (  # noqa: F401 (WgradQueue: re-exported)
+    WgradQueue, _beta, _fold_bias_later, _fp8_grad_bias, _ready, _wgrad)
 from tensorflow_distributed_on_gke_amd.ops import kernels as K
 from tensorflow_distributed_on_gke_amd.ops import fp8, philox
 
 LN_EPS = 1e-6
-# deferred weight gradients as ragged 256x256-tile launches (else per-shape
-# grouped launches of the tile table)
-RAGGED_WGRAD = True
 
 
 @dataclass
@@ -115,239 +115,11 @@ def _keep_scale(rt: RunCtx, site: int, shape, device) -> Optional[torch.Tensor]:
     return keep.to(torch.float32).to(device) / (1.0 - p)
 
 
-def _beta(rt: RunCtx) -> float:
-    return 1.0 if rt.accumulate else 0.0
-
-
-def _ready(rt: RunCtx, *params: Param) -> None:
-    if rt.store is not None:
-        for p in params:
-            rt.store.grad_ready(p)
-
-
 def _write_grad(p: Param, g: torch.Tensor, rt: RunCtx) -> None:
     if rt.accumulate:
         p.grad.add_(g.to(p.grad.dtype))
     else:
         p.grad.copy_(g.to(p.grad.dtype))
-
-
-class WgradQueue:
-    """Weight-gradient GEMMs deferred to the end of backward.
-
-    Nothing in backward reads a weight gradient, so instead of one small
-    long-K GEMM per layer (split-K slabs + a reduce kernel, 64x64 tiles to
-    fill the chip) all of them run as ONE ragged launch of 256x256 whole-K
-    tiles (ops.kernels.wgrad_ragged: 5 shapes, 62 problems, ~730 tiles for
-    Transformer-base; bias gradients fused), or, with RAGGED_WGRAD = False, one
-    grouped launch per shape (ops.kernels.wgrad_grouped) plus column sums.
-    The data-parallel grad_ready notifications follow in backward order."""
-
-    def __init__(self, flush_at_boundary: bool = False, wave_tiles: int = 0):
-        self.items = []
-        # data parallel: also flush when the decoder's backward is complete,
-        # so the decoder-side buckets are all-reduced while the encoder's
-        # backward runs (only without wave chunking)
-        self.flush_at_boundary = flush_at_boundary
-        # data parallel, ragged path: at every layer end launch as many whole
-        # waves of `wave_tiles` tiles (one 256x256 whole-K tile per CU) as are
-        # queued -- a launch of the queue's first n*wave_tiles tiles, cutting
-        # the boundary problem by tile range -- so the all-reduce of those
-        # gradients starts layers earlier while the launches together cost
-        # exactly the waves of a single launch (chunks that each fill only
-        # part of a wave cost a whole wave each: 4 chunks measured 1004 us vs
-        # 745 us for one launch on Transformer-base)
-        self.wave_tiles = wave_tiles
-        # layer_end() calls per backward (set by the owner: encoder + decoder
-        # layers). With wave chunking the LAST layer end flushes everything
-        # queued, partial wave included: otherwise the remainder waits for the
-        # end of backward and its gradients join the embedding gradients in
-        # the final, fully exposed all-reduce span (71 MB at Transformer-base;
-        # with the full flush the final span holds little more than the
-        # source embedding)
-        self.layers_per_step = 0
-        self._layer_ends = 0
-        self._cursor = 0  # tiles of items[0] already launched
-        # deferred LayerNorm dgamma/dbeta/bias partial folds (one launch per flush)
-        self.reductions = []
-        self.reduced_params = []
-        self.fp8_items = []
-        self.small_per_shape = False
-
-    def boundary(self) -> None:
-        if self.flush_at_boundary and not self._chunking() and (self.items or self.reductions or self.fp8_items):
-            self.flush()
-
-    @staticmethod
-    def _tiles(it) -> int:
-        dy2, x2, N = it[0], it[1], it[2]
-        return -(-N // 256) * -(-x2.shape[1] // 256)
-
-    @staticmethod
-    def _ragged_ok(it) -> bool:
-        dy2, x2 = it[0], it[1]
-        return x2.shape[0] % 64 == 0 and dy2.stride(0) % 8 == 0 and x2.stride(0) % 8 == 0
-
-    def _chunking(self) -> bool:
-        return bool(self.wave_tiles) and RAGGED_WGRAD
-
-    def layer_end(self) -> None:
-        """A decoder or encoder layer's backward is complete."""
-        self._layer_ends += 1
-        last = self.layers_per_step > 0 and self._layer_ends >= self.layers_per_step
-        if self._chunking() and self.fp8_items:
-            self._flush_fp8()  # (its gradients join the next all-reduce span)
-        if not self._chunking() or not self.items:
-            return
-        if last or not all(self._ragged_ok(it) for it in self.items):
-            self.flush()
-            return
-        queued = sum(self._tiles(it) for it in self.items) - self._cursor
-        n = queued // self.wave_tiles * self.wave_tiles
-        if n:
-            self._launch_prefix(n)
-            self._finish_flush()
-
-    def add(self, dy2, x2, N, w: Param, b: Optional[Param], beta: float, rt: "RunCtx"):
-        self.items.append((dy2, x2, N, w, b, beta, rt))
-
-    def add_fp8(self, dy8, sa, x8, sb, w: Param, beta: float, rt: "RunCtx"):
-        """An fp8 weight gradient (ops.fp8.wgrad_fp8), launched with the
-        next flush / layer end as one ragged fp8 launch."""
-        self.fp8_items.append((dy8, sa, x8, sb, w, beta, rt))
-
-    def _flush_fp8(self) -> None:
-        if not self.fp8_items:
-            return
-        by_beta = {}
-        for it in self.fp8_items:
-            by_beta.setdefault(it[5], []).append(it)
-        for beta, its in by_beta.items():
-            # equal shapes adjacent (one class each)
-            its.sort(key=lambda it: (it[4].shape, it[0].stride(0), it[2].stride(0)))
-            fp8.wgrad_fp8([it[0] for it in its], [it[1] for it in its], [it[2] for it in its],
-                          [it[3] for it in its], [it[4].grad for it in its], beta)
-        for it in self.fp8_items:
-            _ready(it[6], it[4])
-        self.fp8_items = []
-
-    def step_done(self) -> None:
-        """End of a backward: the layer-end count restarts."""
-        self._layer_ends = 0
-
-    def flush(self) -> None:
-        self._flush_fp8()
-        if self.items:
-            # (small_per_shape: a flush of under half a wave of 256x256 tiles
-            # -- the fp8 step's lone bf16 vocab projection -- runs per shape
-            # on 128x128 tiles)
-            if RAGGED_WGRAD and all(self._ragged_ok(it) for it in self.items) and (
-                    not self.small_per_shape or self._cursor
-                    or sum(self._tiles(it) for it in self.items) >= K.NUM_CU // 2):
-                self._launch_prefix(sum(self._tiles(it) for it in self.items) - self._cursor)
-            else:  # (never partially launched: chunking needs the ragged path)
-                self._flush_grouped()
-                self._flush_bias()
-                self._done = self.items
-                self.items = []
-        else:
-            self._done = []
-        self._finish_flush()
-
-    def _finish_flush(self) -> None:
-        if self.reductions:
-            K.reduce_partials_multi(self.reductions)
-        done = getattr(self, "_done", [])
-        for dy2, x2, N, w, b, beta, rt in done:
-            _ready(rt, w, *([b] if b is not None else []))
-        for rt, p in self.reduced_params:
-            _ready(rt, p)
-        rts = [it[6] for it in done] + [rp[0] for rp in self.reduced_params]
-        if rts and rts[0].store is not None:
-            rts[0].store.grad_sync()
-        self._done = []
-        self.reductions = []
-        self.reduced_params = []
-
-    def _launch_prefix(self, n: int) -> None:
-        """Launch the first n not-yet-launched tiles of the queue (whole-K
-        256x256 tiles, bias gradients fused): the items they complete move to
-        self._done; a cut item stays at the queue head with self._cursor set."""
-        sel = []  # (item, t_first, t_count)
-        done = []
-        left = n
-        while left > 0 and self.items:
-            it = self.items[0]
-            avail = self._tiles(it) - self._cursor
-            take = min(avail, left)
-            sel.append((it, self._cursor, take))
-            left -= take
-            if take == avail:
-                done.append(self.items.pop(0))
-                self._cursor = 0
-            else:
-                self._cursor += take
-        self._done = done
-        # one launch per (token count, beta); within it full problems of equal
-        # shape adjacent (one class each), cut problems as classes of their own
-        runs = {}
-        for it, first, cnt in sel:
-            dy2, x2, N, w, b, beta, rt = it
-            full = first == 0 and cnt == self._tiles(it)
-            key = (N, x2.shape[1], dy2.stride(0), x2.stride(0)) if full else ("cut", id(it), first)
-            runs.setdefault((x2.shape[0], beta), {}).setdefault(key, []).append((it, first, cnt))
-        for (_, beta), by_shape in runs.items():
-            groups = list(by_shape.values())
-            for s0 in range(0, len(groups), K.RAGGED_MAX_SHAPES):
-                chunk = [e for grp in groups[s0:s0 + K.RAGGED_MAX_SHAPES] for e in grp]
-                for c0 in range(0, len(chunk), K.RAGGED_MAX_PROBLEMS):
-                    part = chunk[c0:c0 + K.RAGGED_MAX_PROBLEMS]
-                    K.wgrad_ragged([e[0][0] for e in part], [e[0][1] for e in part],
-                                   [e[0][3].grad for e in part], beta,
-                                   [e[0][4].grad if e[0][4] is not None else None for e in part],
-                                   ranges=[(e[1], e[2]) for e in part])
-
-    def _flush_grouped(self) -> None:
-        groups = {}
-        for it in self.items:
-            dy2, x2, N, w, b, beta, rt = it
-            key = (tuple(dy2.shape), dy2.stride(0), tuple(x2.shape), x2.stride(0), N, beta)
-            groups.setdefault(key, []).append(it)
-        for key, items in groups.items():
-            for c0 in range(0, len(items), 32):
-                chunk = items[c0:c0 + 32]
-                beta = chunk[0][5]
-                if len(chunk) == 1:
-                    dy2, x2, N, w, *_ = chunk[0]
-                    K.linear_wgrad(dy2, x2, N, w.grad, beta)
-                else:
-                    K.wgrad_grouped([i[0] for i in chunk], [i[1] for i in chunk],
-                                    [i[3].grad for i in chunk], beta)
-
-    def _flush_bias(self) -> None:
-        bgroups = {}
-        for dy2, x2, N, w, b, beta, rt in self.items:
-            if b is not None:
-                bgroups.setdefault((tuple(dy2.shape), dy2.stride(0), N, beta), []).append((dy2, b))
-        for (shape, ld, N, beta), items in bgroups.items():
-            for c0 in range(0, len(items), 32):
-                chunk = items[c0:c0 + 32]
-                if len(chunk) == 1:
-                    K.colsum(chunk[0][0], N, chunk[0][1].grad, beta)
-                else:
-                    K.colsum_grouped([i[0] for i in chunk], [i[1].grad for i in chunk], beta)
-
-
-def _wgrad(rt: RunCtx, dy2, x2, N: int, w: Param, b: Optional[Param] = None) -> None:
-    """dW (+ bias grad) of a Linear on the GPU: deferred (rt.wgrad) or now."""
-    bt = _beta(rt)
-    if rt.wgrad is not None:
-        rt.wgrad.add(dy2, x2, N, w, b, bt, rt)
-        return
-    K.linear_wgrad(dy2, x2, N, w.grad, bt)
-    if b is not None:
-        K.colsum(dy2, N, b.grad, bt)
-    _ready(rt, w, *([b] if b is not None else []))
 
 
 def _attn_lean(rt: RunCtx, M: int, w_in: Param, w_out: Optional[Param], d: int) -> bool:
@@ -359,42 +131,15 @@ def _attn_lean(rt: RunCtx, M: int, w_in: Param, w_out: Optional[Param], d: int) 
             and fp8.wgrad_fp8_ok(M, d, d))
 
 
-def _fp8_grad_bias(g: torch.Tensor, g_slot: int, b: Param, rt: RunCtx, key: str):
-    """e5m2 copy of the bf16 gradient g [M, N] and, from the same pass, the
-    bias gradient (column sums) -- folded with the queue's other deferred
-    column reductions at the next flush (one launch)."""
-    st = rt.fp8
-    g8, part, nparts = fp8.quantize_colsum(g, st.gmeta, g_slot, key)
-    q = rt.wgrad
-    q.reductions.append((part, b.grad, nparts, g.shape[1], _beta(rt)))
-    q.reduced_params.append((rt, b))
-    return g8
-
-
-def _fold_bias_later(rt: RunCtx, part: torch.Tensor, nparts: int, N: int, b: Param) -> None:
-    """b's gradient = column sums of the [nparts, N] partials, folded with the
-    queue's other deferred column reductions at the next flush."""
-    q = rt.wgrad
-    q.reductions.append((part, b.grad, nparts, N, _beta(rt)))
-    q.reduced_params.append((rt, b))
-
-
-def _fp8_dgrad_into(g8, g_slot: int, w: Param, out: torch.Tensor, rt: RunCtx, beta: float) -> None:
+def _fp8_dgrad(g8, g_slot: int, w: Param, out, rt: RunCtx, beta: float = 0.0, out8_slot=None):
     """out (=|+= beta) dequant(g8 (e5m2) @ w) against w's e4m3 copy (read
-    N-contiguous by the kernel, fp8.DGRAD_PLAIN_W; else its transposed copy)."""
+    N-contiguous by the kernel, fp8.DGRAD_PLAIN_W; else its transposed copy).
+    out None, out8_slot: returns its e5m2 copy only (no bf16 output) in that
+    gradient slot (amax recorded): the fp8 attention backward's dO."""
     st = rt.fp8
     wt8, swt = st.weights.get(w, transposed=not fp8.DGRAD_PLAIN_W)
-    fp8.gemm_bf8_dgrad(g8, st.gmeta, g_slot, wt8, st.meta, swt, out, beta=beta,
-                       w_plain=fp8.DGRAD_PLAIN_W)
-
-
-def _fp8_dgrad8(g8, g_slot: int, w: Param, out_slot: int, rt: RunCtx) -> torch.Tensor:
-    """e5m2 copy only (no bf16 output) of dequant(g8 (e5m2) @ w) in the
-    gradient slot out_slot (amax recorded): the fp8 attention backward's dO."""
-    st = rt.fp8
-    wt8, swt = st.weights.get(w, transposed=not fp8.DGRAD_PLAIN_W)
-    return fp8.gemm_bf8_dgrad(g8, st.gmeta, g_slot, wt8, st.meta, swt, None, out8_slot=out_slot,
-                              w_plain=fp8.DGRAD_PLAIN_W)
+    return fp8.gemm_bf8_dgrad(g8, st.gmeta, g_slot, wt8, st.meta, swt, out, beta=beta,
+                              out8_slot=out8_slot, w_plain=fp8.DGRAD_PLAIN_W)
 
 
 def _f8_bwd_planned(rt: RunCtx, lean: bool, Lq: int, Lk: int, hd: int) -> bool:
@@ -403,12 +148,6 @@ def _f8_bwd_planned(rt: RunCtx, lean: bool, Lq: int, Lk: int, hd: int) -> bool:
     outputs are never read and not written. (Not with attention maps: they
     read the bf16 Q / K.)"""
     return (lean and fp8.ATTN_BWD_F8 and rt.attn_maps is None and K.attn_bwd_f8_ok(Lq, Lk, hd))
-
-
-def _attn_f8_bwd(ctx, Lq: int, Lk: int, hd: int) -> bool:
-    """Does this attention block's fp8 backward run on the fp8 kernel (its
-    forward decided so: _f8_bwd_planned, and kept the e4m3 operands)?"""
-    return getattr(ctx, "f8b", False) and getattr(ctx, "q8", None) is not None
 
 
 # =============================================================================== LN helpers
@@ -474,14 +213,15 @@ def _ln_bwd(dy, saved, gamma: Param, beta: Param, sub_bias: Param, site: int, rt
             gm = rt.fp8.gmeta
             ds8 = torch.empty(dy.shape, dtype=gm.dtype, device=dy.device)
             s8, a8 = gm.s(ds8_slot), gm.a(ds8_slot)
+        folds = [] if q is not None else None
         dh, ds = K.ln_bwd(dy.contiguous(), h, mean, rstd, gamma.master, gamma.grad, beta.grad,
                           sub_bias.grad, rt.p, rt.seed, rt.ctr, site, want_ds=ds8 is None,
-                          accumulate=rt.accumulate, defer=q.reductions if q is not None else None,
+                          accumulate=rt.accumulate, defer=folds,
                           ds8=ds8, s8=s8, amax8=a8, kbits=saved[4])
         if ds8 is not None:
             ds = ds8
         if q is not None:  # folded (and reported ready) with the next wgrad flush
-            q.reduced_params += [(rt, gamma), (rt, beta), (rt, sub_bias)]
+            q.defer_fold(folds, (gamma, beta, sub_bias), rt)
             return dh, ds
     else:
         xhat = (h - mean) * rstd
@@ -506,6 +246,7 @@ def _dgrad_into(dy2: torch.Tensor, w: Param, N: int, dx: torch.Tensor) -> torch.
 
 # =============================================================================== embedding
 class EmbedFn(torch.autograd.Function):
+    NO_GRAD_ARGS = 6  # forward arguments that get no gradient from backward: all of them
     @staticmethod
     def forward(ctx, anchor, tok, table: Param, pe: torch.Tensor, site: int, rt: RunCtx):
         d = table.shape[1]
@@ -534,14 +275,12 @@ class EmbedFn(torch.autograd.Function):
             dc = dout.contiguous()
             K.embed_bwd(tok, dc, table.grad, ctx.scale, rt.p, rt.seed, rt.ctr, ctx.site,
                         accumulate=rt.accumulate, kbits=ctx.kbits, csr=ctx.csr)
-            _ready(rt, table)
-            return None, None, None, None, None, None
         else:
             g = dout * ctx.ks if ctx.ks is not None else dout
             g = (g * ctx.scale).reshape(-1, table.shape[1])
             table.grad.index_add_(0, tok.reshape(-1), g.to(table.grad.dtype))
         _ready(rt, table)
-        return None, None, None, None, None, None
+        return (None,) * EmbedFn.NO_GRAD_ARGS
 
 
 # =============================================================================== attention (CPU reference core)
@@ -578,8 +317,50 @@ def attention_probs(q, k, kv_len, causal: bool, scale: float) -> torch.Tensor:
     return _ref_attn_fwd(q, k, k, kv_len, causal, scale)[1]
 
 
+def _attn_out_ln_fwd(ctx, o, s, x, wo: Param, bo: Param, gamma: Param, beta: Param, site: int,
+                     rt: RunCtx, kx, o8e):
+    """An attention block's forward ending y = LN(x + dropout(o @ Wo^T + bo)) (s: that projection,
+    where the CPU reference computed it); sets ctx.ln and ctx.f8a. kx, o8e: the lean block's
+    kept e4m3 input and the e4m3 O its attention epilogue emitted."""
+    M, d = x.numel() // x.shape[-1], x.shape[-1]
+    ctx.f8a = None
+    if ctx.lean:  # e4m3 output projection; keep the e4m3 operands for the backward
+        s, o8 = rt.fp8.out_proj(o.view(M, d), wo, bo, o8e[0] if o8e else None)
+        ctx.f8a = (kx[0], kx[1], o8)
+        y, ctx.ln = _ln_fwd(x, s.view(x.shape), gamma, beta, site, rt)
+    elif s is None:
+        y, ctx.ln = _proj_ln_fwd(o.view(M, d), wo, bo, x, gamma, beta, site, rt)
+    else:
+        y, ctx.ln = _ln_fwd(x, s.view(x.shape), gamma, beta, site, rt)
+    return y
+
+
+_LeanBwd = namedtuple("_LeanBwd", "dh ds8 go os_ gq x8 xs o8")
+
+
+def _lean_bwd_begin(ctx, dy, w_in: Param, site: int, rt: RunCtx) -> _LeanBwd:
+    """Start of a lean fp8 attention backward (ctx.p = (w_in, b_in, wo, bo, gamma, beta)): the
+    LayerNorm backward -> dh and ds [M, d] as e5m2 only (gradient slot go); gq: w_in's gradient
+    slot; x8 (slot xs), o8 (slot os_): the forward's e4m3 block input and attention output."""
+    wo, bo, gamma, beta = ctx.p[2:]
+    st = rt.fp8
+    x8, xs, o8 = ctx.f8a
+    os_, go = st.attn_out[id(wo)]
+    dh, ds8 = _ln_bwd(dy, ctx.ln, gamma, beta, bo, site, rt, ds8_slot=go)
+    return _LeanBwd(dh, ds8.view(-1, dy.shape[-1]), go, os_, st.proj_bwd[id(w_in)], x8, xs, o8)
+
+
+def _lean_bwd_end(lb: _LeanBwd, g8, w_in: Param, wo: Param, rt: RunCtx) -> None:
+    """input-projection dgrad of e5m2 g8 into the residual gradient, both weight gradients in fp8"""
+    st, bt = rt.fp8, _beta(rt)
+    _fp8_dgrad(g8, lb.gq, w_in, lb.dh.view(lb.ds8.shape), rt, 1.0)
+    rt.wgrad.add_fp8(lb.ds8, st.gmeta.s(lb.go), lb.o8, st.meta.s(lb.os_), wo, bt, rt)
+    rt.wgrad.add_fp8(g8, st.gmeta.s(lb.gq), lb.x8, st.meta.s(lb.xs), w_in, bt, rt)
+
+
 # =============================================================================== self-attention block
 class SelfAttnBlockFn(torch.autograd.Function):
+    NO_GRAD_ARGS = 11  # forward arguments after x
     @staticmethod
     def forward(ctx, x, wqkv: Param, bqkv: Param, wo: Param, bo: Param, gamma: Param,
                 beta: Param, heads: int, kv_len, causal: bool, site: int, rt: RunCtx):
@@ -591,6 +372,7 @@ class SelfAttnBlockFn(torch.autograd.Function):
         x2 = x.reshape(B * L, d)
         ctx.lean = lean = x.is_cuda and _attn_lean(rt, B * L, wqkv, wo, d)
         kx = [] if lean else None
+        o8e = None
         if x.is_cuda:
             f8 = rt.fp8 is not None and K.attn_fwd_fp8_ok(L, L, hd)
             # the fp8 backward reads only the e4m3 Q|K|V: no bf16 copy then
@@ -607,7 +389,6 @@ class SelfAttnBlockFn(torch.autograd.Function):
             if qkv is None and not ctx.f8b:
                 qkv = K.linear_fwd(x2, wqkv.compute, bqkv.master)  # [M, 3d]
             q5 = qkv.view(B, L, 3, heads, hd) if qkv is not None else None
-            o8e = None
             ctx.q8 = None
             if fused is not None:
                 o, aux = fused[1], fused[2]
@@ -629,29 +410,19 @@ class SelfAttnBlockFn(torch.autograd.Function):
             s = o.reshape(B * L, d) @ wo.master.t() + bo.master
         if rt.attn_maps is not None:  # (_f8_bwd_planned: q5 exists when maps are asked for)
             rt.attn_maps[site] = attention_probs(q5[:, :, 0], q5[:, :, 1], kv_len, causal, scale)
-        ctx.f8a = None
-        if lean:  # e4m3 output projection; keep the e4m3 operands for the backward
-            s, o8 = rt.fp8.out_proj(o.view(B * L, d), wo, bo, o8e[0] if o8e else None)
-            ctx.f8a = (kx[0], kx[1], o8)
-            y, ctx.ln = _ln_fwd(x, s.view(B, L, d), gamma, beta, site, rt)
-        elif s is None:
-            y, ctx.ln = _proj_ln_fwd(o.view(B * L, d), wo, bo, x, gamma, beta, site, rt)
-        else:
-            y, ctx.ln = _ln_fwd(x, s.view(B, L, d), gamma, beta, site, rt)
+        y = _attn_out_ln_fwd(ctx, o, s, x, wo, bo, gamma, beta, site, rt, kx, o8e)
         ctx.save_for_backward(x2, qkv, o, aux, kv_len)
         return y
 
     @staticmethod
     def backward(ctx, dy):
+        if ctx.lean:
+            return SelfAttnBlockFn._backward_fp8(ctx, dy)
         wqkv, bqkv, wo, bo, gamma, beta = ctx.p
         heads, causal, scale, site, rt = ctx.meta
         x2, qkv, o, aux, kv_len = ctx.saved_tensors
         B, L, d = dy.shape
-        M = B * L
-        hd = d // heads
-        bt = _beta(rt)
-        if ctx.lean:
-            return SelfAttnBlockFn._backward_fp8(ctx, dy)
+        M, hd = B * L, d // heads
         dh, ds = _ln_bwd(dy, ctx.ln, gamma, beta, bo, site, rt)
         ds2 = ds.reshape(M, d)
         q5 = qkv.view(B, L, 3, heads, hd)
@@ -667,10 +438,6 @@ class SelfAttnBlockFn(torch.autograd.Function):
                 K.attn_bwd(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], o, do.view(B, L, heads, hd), aux,
                            g5[:, :, 0], g5[:, :, 1], g5[:, :, 2], kv_len, scale, causal)
             _wgrad(rt, dqkv, x2, 3 * d, wqkv, bqkv)
-            dx = _dgrad_res(dqkv, wqkv, 3 * d, dh)
-            if rt.wgrad is not None:
-                rt.wgrad.layer_end()  # self-attention is a layer's first block
-            return (dx.view(B, L, d),) + (None,) * 11
         else:
             _write_grad(wo, ds2.t() @ o.reshape(M, d), rt)
             _ready(rt, wo)
@@ -679,9 +446,11 @@ class SelfAttnBlockFn(torch.autograd.Function):
             dqkv = torch.stack([dq, dk, dv], dim=2).reshape(M, 3 * d)
             _write_grad(wqkv, dqkv.t() @ x2, rt)
             _write_grad(bqkv, dqkv.sum(0), rt)
-        _ready(rt, wqkv, bqkv)
+            _ready(rt, wqkv, bqkv)  # (GPU: reported by _wgrad / the deferred flush)
         dx = _dgrad_into(dqkv, wqkv, 3 * d, dh)
-        return (dx.view(B, L, d),) + (None,) * 11
+        if dy.is_cuda and rt.wgrad is not None:
+            rt.wgrad.layer_end()  # self-attention is a layer's first block
+        return (dx.view(B, L, d),) + (None,) * SelfAttnBlockFn.NO_GRAD_ARGS
 
     @staticmethod
     def _backward_fp8(ctx, dy):
@@ -689,22 +458,19 @@ class SelfAttnBlockFn(torch.autograd.Function):
         dgrad (e5m2 x e4m3 Wo^T) -> bf16 attention backward -> e5m2 dQ|dK|dV
         -> input-projection dgrad (into the residual gradient); both weight
         gradients in fp8 from the saved e4m3 operands."""
-        wqkv, bqkv, wo, bo, gamma, beta = ctx.p
+        wqkv, bqkv, wo = ctx.p[:3]
         heads, causal, scale, site, rt = ctx.meta
         x2, qkv, o, aux, kv_len = ctx.saved_tensors
         B, L, d = dy.shape
-        M, hd, bt = B * L, d // heads, _beta(rt)
+        M, hd = B * L, d // heads
         st = rt.fp8
-        x8, xs, o8 = ctx.f8a
-        os_, go = st.attn_out[id(wo)]
-        dh, ds8 = _ln_bwd(dy, ctx.ln, gamma, beta, bo, site, rt, ds8_slot=go)
-        ds8 = ds8.view(M, d)
-        gq = st.proj_bwd[id(wqkv)]
-        if _attn_f8_bwd(ctx, L, L, hd):
+        lb = _lean_bwd_begin(ctx, dy, wqkv, site, rt)
+        ds8, go, gq = lb.ds8, lb.go, lb.gq
+        if ctx.f8b and ctx.q8 is not None:  # (planned by the forward, which kept the e4m3 operands)
             # fp8 attention backward: e5m2 dO straight from the output
             # projection's dgrad, e4m3 Q/K/V of the forward -> e5m2 dQ|dK|dV
             gdo, gds = st.attn_bwd8[id(wo)]
-            do8 = _fp8_dgrad8(ds8, go, wo, gdo, rt)
+            do8 = _fp8_dgrad(ds8, go, wo, None, rt, out8_slot=gdo)
             qkv8, qs = ctx.q8
             q85 = qkv8.view(B, L, 3, heads, hd)
             s8 = st.meta.s(qs)
@@ -718,42 +484,31 @@ class SelfAttnBlockFn(torch.autograd.Function):
                                    amaxg8=st.gmeta.a(gq), cs_part=part, cs_ld=3 * d, cs_q=0,
                                    cs_k=d, cs_v=2 * d)
             _fold_bias_later(rt, part[: nparts * 3 * d], nparts, 3 * d, bqkv)
-            return SelfAttnBlockFn._finish_fp8(ctx, rt, st, dh, ds8, go, dqkv8, gq, x8, xs, o8, os_,
-                                               M, d, B, L, bt)
-        do = torch.empty(M, d, dtype=torch.bfloat16, device=dy.device)
-        _fp8_dgrad_into(ds8, go, wo, do, rt, 0.0)
-        q5 = qkv.view(B, L, 3, heads, hd)
-        dqkv = torch.empty(M, 3 * d, dtype=torch.bfloat16, device=dy.device)
-        g5 = dqkv.view(B, L, 3, heads, hd)
-        if fp8.ATTN_BWD_G8 and K.attn_bwd_g8_ok(L, L, hd):
-            # the attention backward emits e5m2 dQ|dK|dV, their amax and the
-            # bias-gradient partials itself (no bf16 dQ|dK|dV pass)
-            dqkv8 = torch.empty(M, 3 * d, dtype=st.gmeta.dtype, device=dy.device)
-            g85 = dqkv8.view(B, L, 3, heads, hd)
-            part = K.workspace(f"qcs_qkv{site}", B * -(-L // 128) * 3 * d, dy.device)
-            nparts = K.attn_bwd_g8(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], o, do.view(B, L, heads, hd),
-                                   aux, g5[:, :, 0], g5[:, :, 1], g5[:, :, 2], kv_len, scale, causal,
-                                   g85[:, :, 0], g85[:, :, 1], g85[:, :, 2], st.gmeta.s(gq),
-                                   st.gmeta.a(gq), part, 3 * d, 0, d, 2 * d)
-            _fold_bias_later(rt, part[: nparts * 3 * d], nparts, 3 * d, bqkv)
         else:
-            K.attn_bwd(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], o, do.view(B, L, heads, hd), aux,
-                       g5[:, :, 0], g5[:, :, 1], g5[:, :, 2], kv_len, scale, causal)
-            dqkv8 = _fp8_grad_bias(dqkv, gq, bqkv, rt, f"qkv{site}")
-        return SelfAttnBlockFn._finish_fp8(ctx, rt, st, dh, ds8, go, dqkv8, gq, x8, xs, o8, os_, M,
-                                           d, B, L, bt)
-
-    @staticmethod
-    def _finish_fp8(ctx, rt, st, dh, ds8, go, dqkv8, gq, x8, xs, o8, os_, M, d, B, L, bt):
-        """input-projection dgrad into the residual gradient, both weight
-        gradients in fp8"""
-        wqkv, bqkv, wo = ctx.p[0], ctx.p[1], ctx.p[2]
-        _fp8_dgrad_into(dqkv8, gq, wqkv, dh.view(M, d), rt, 1.0)
-        q = rt.wgrad
-        q.add_fp8(ds8, st.gmeta.s(go), o8, st.meta.s(os_), wo, bt, rt)
-        q.add_fp8(dqkv8, st.gmeta.s(gq), x8, st.meta.s(xs), wqkv, bt, rt)
-        q.layer_end()  # self-attention is a layer's first block
-        return (dh.view(B, L, d),) + (None,) * 11
+            do = torch.empty(M, d, dtype=torch.bfloat16, device=dy.device)
+            _fp8_dgrad(ds8, go, wo, do, rt, 0.0)
+            q5 = qkv.view(B, L, 3, heads, hd)
+            dqkv = torch.empty(M, 3 * d, dtype=torch.bfloat16, device=dy.device)
+            g5 = dqkv.view(B, L, 3, heads, hd)
+            if fp8.ATTN_BWD_G8 and K.attn_bwd_g8_ok(L, L, hd):
+                # the attention backward emits e5m2 dQ|dK|dV, their amax and the
+                # bias-gradient partials itself (no bf16 dQ|dK|dV pass)
+                dqkv8 = torch.empty(M, 3 * d, dtype=st.gmeta.dtype, device=dy.device)
+                g85 = dqkv8.view(B, L, 3, heads, hd)
+                part = K.workspace(f"qcs_qkv{site}", B * -(-L // 128) * 3 * d, dy.device)
+                nparts = K.attn_bwd_g8(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], o,
+                                       do.view(B, L, heads, hd), aux, g5[:, :, 0], g5[:, :, 1],
+                                       g5[:, :, 2], kv_len, scale, causal, g85[:, :, 0], g85[:, :, 1],
+                                       g85[:, :, 2], st.gmeta.s(gq), st.gmeta.a(gq), part, 3 * d, 0, d,
+                                       2 * d)
+                _fold_bias_later(rt, part[: nparts * 3 * d], nparts, 3 * d, bqkv)
+            else:
+                K.attn_bwd(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], o, do.view(B, L, heads, hd), aux,
+                           g5[:, :, 0], g5[:, :, 1], g5[:, :, 2], kv_len, scale, causal)
+                dqkv8 = _fp8_grad_bias(dqkv, gq, bqkv, rt, f"qkv{site}")
+        _lean_bwd_end(lb, dqkv8, wqkv, wo, rt)
+        rt.wgrad.layer_end()  # self-attention is a layer's first block
+        return (lb.dh.view(B, L, d),) + (None,) * SelfAttnBlockFn.NO_GRAD_ARGS
 
 
 # =============================================================================== cross-attention
@@ -769,6 +524,7 @@ class CrossKVFn(torch.autograd.Function):
     """kv_all[B, S, layers*2*d] = enc @ Wkv_all^T + b: the K and V projections
     of the encoder output for every decoder layer in one GEMM."""
 
+    NO_GRAD_ARGS = 4  # forward arguments after enc
     @staticmethod
     def forward(ctx, enc, wkv: Param, bkv: Param, kvh: KVGrad, rt: RunCtx):
         B, S, d = enc.shape
@@ -831,10 +587,10 @@ class CrossKVFn(torch.autograd.Function):
             rt.wgrad.add_fp8(dkv8, st.gmeta.s(gk), x8, st.meta.s(xs), wkv, bt, rt)
             rt.wgrad.boundary()
             denc = torch.empty(B * S, d, dtype=torch.bfloat16, device=e2.device)
-            _fp8_dgrad_into(dkv8, gk, wkv, denc, rt, 0.0)
+            _fp8_dgrad(dkv8, gk, wkv, denc, rt, 0.0)
             if rt.store is not None:
                 rt.store.release_point()
-            return denc.view(B, S, d), None, None, None, None
+            return (denc.view(B, S, d),) + (None,) * CrossKVFn.NO_GRAD_ARGS
         dkv = _take_dkv(dkv_in, kvh, B * S)
         if e2.is_cuda:
             _wgrad(rt, dkv, e2, N, wkv, bkv)
@@ -850,13 +606,14 @@ class CrossKVFn(torch.autograd.Function):
             # the rest of backward (encoder) reads no decoder-side weight: the
             # data-parallel optimizer may update those buckets from here on
             rt.store.release_point()
-        return denc.view(B, S, d), None, None, None, None
+        return (denc.view(B, S, d),) + (None,) * CrossKVFn.NO_GRAD_ARGS
 
 
 class CrossAttnBlockFn(torch.autograd.Function):
     """Decoder block 2: Q from the decoder stream, K = V = encoder output
     (reference call order mha2(enc, enc, out1) -> values, keys, query)."""
 
+    NO_GRAD_ARGS = 12  # forward arguments after x and kv_all
     @staticmethod
     def forward(ctx, x, kv_all, layer: int, kvh: KVGrad, wq: Param, bq: Param, wo: Param,
                 bo: Param, gamma: Param, beta: Param, heads: int, kv_len, site: int, rt: RunCtx):
@@ -874,8 +631,8 @@ class CrossAttnBlockFn(torch.autograd.Function):
             kv5 = kv_all[:, :, layer * 2 * d:(layer + 1) * 2 * d].view(B, S, 2, heads, hd)
         ctx.lean = lean = x.is_cuda and _attn_lean(rt, B * T, wq, wo, d)
         kx = [] if lean else None
+        o8e = None
         if x.is_cuda:
-            o8e = None
             f8 = (rt.fp8 is not None and rt.fp8.kv8 is not None and K.attn_fwd_fp8_ok(T, S, hd))
             ctx.f8b = f8 and _f8_bwd_planned(rt, lean, T, S, hd)
             if kvh.f8b and not ctx.f8b:
@@ -919,15 +676,7 @@ class CrossAttnBlockFn(torch.autograd.Function):
             s = o.reshape(B * T, d) @ wo.master.t() + bo.master
         if rt.attn_maps is not None:  # (_f8_bwd_planned: q exists when maps are asked for)
             rt.attn_maps[site] = attention_probs(q.view(B, T, heads, hd), kv5[:, :, 0], kv_len, False, scale)
-        ctx.f8a = None
-        if lean:  # e4m3 output projection; keep the e4m3 operands for the backward
-            s, o8 = rt.fp8.out_proj(o.view(B * T, d), wo, bo, o8e[0] if o8e else None)
-            ctx.f8a = (kx[0], kx[1], o8)
-            y, ctx.ln = _ln_fwd(x, s.view(B, T, d), gamma, beta, site, rt)
-        elif s is None:
-            y, ctx.ln = _proj_ln_fwd(o.view(B * T, d), wo, bo, x, gamma, beta, site, rt)
-        else:
-            y, ctx.ln = _ln_fwd(x, s.view(B, T, d), gamma, beta, site, rt)
+        y = _attn_out_ln_fwd(ctx, o, s, x, wo, bo, gamma, beta, site, rt, kx, o8e)
         ctx.save_for_backward(x2, kv_all, q, o, aux, kv_len)
         return y
 
@@ -938,9 +687,7 @@ class CrossAttnBlockFn(torch.autograd.Function):
         x2, kv_all, q, o, aux, kv_len = ctx.saved_tensors
         B, T, d = dy.shape
         S = kv_all.shape[1]
-        hd = d // heads
-        bt = _beta(rt)
-        M = B * T
+        M, hd = B * T, d // heads
         if kvh.f8b:
             # every layer's d(K|V) goes to kvh.buf8 as e5m2: autograd gets a
             # zero-stride placeholder of the right shape, no bf16 buffer
@@ -953,17 +700,14 @@ class CrossAttnBlockFn(torch.autograd.Function):
             g5 = dkv_all[:, :, layer * 2 * d:(layer + 1) * 2 * d].view(B, S, 2, heads, hd)
         if ctx.lean:
             st = rt.fp8
-            x8, xs, o8 = ctx.f8a
-            os_, go = st.attn_out[id(wo)]
-            dh, ds8 = _ln_bwd(dy, ctx.ln, gamma, beta, bo, site, rt, ds8_slot=go)
-            ds8 = ds8.view(M, d)
-            gq = st.proj_bwd[id(wq)]
-            if _attn_f8_bwd(ctx, T, S, hd):
+            lb = _lean_bwd_begin(ctx, dy, wq, site, rt)
+            dh, ds8, go, gq = lb.dh, lb.ds8, lb.go, lb.gq
+            if ctx.f8b and ctx.q8 is not None:  # (planned by the forward, which kept the e4m3 operands)
                 # fp8 attention backward: e5m2 dQ (+ amax, bias sums); dK / dV
                 # as e5m2 into kvh.buf8 (kvh.f8b) or bf16 into the batched
                 # cross K|V gradient
                 gdo, gds = st.attn_bwd8[id(wo)]
-                do8 = _fp8_dgrad8(ds8, go, wo, gdo, rt)
+                do8 = _fp8_dgrad(ds8, go, wo, None, rt, out8_slot=gdo)
                 q8, qs, kv85, kvs = ctx.q8
                 skv = st.meta.s(kvs)
                 dq8 = torch.empty(M, d, dtype=st.gmeta.dtype, device=dy.device)
@@ -989,39 +733,33 @@ class CrossAttnBlockFn(torch.autograd.Function):
                                        sg8=st.gmeta.s(gq), amaxg8=st.gmeta.a(gq), cs_part=part,
                                        cs_ld=d, cs_q=0, **kvo)
                 _fold_bias_later(rt, part[: nparts * d], nparts, d, bq)
-                _fp8_dgrad_into(dq8, gq, wq, dh.view(M, d), rt, 1.0)
-                rt.wgrad.add_fp8(ds8, st.gmeta.s(go), o8, st.meta.s(os_), wo, bt, rt)
-                rt.wgrad.add_fp8(dq8, st.gmeta.s(gq), x8, st.meta.s(xs), wq, bt, rt)
-                dkv_ret = None
-                if layer == 0:
-                    dkv_ret = dkv_all if dkv_all is not None else torch.zeros(
-                        1, dtype=kv_all.dtype, device=dy.device).expand(kv_all.shape)
-                return (dh.view(B, T, d), dkv_ret) + (None,) * 12
-            do = torch.empty(M, d, dtype=torch.bfloat16, device=dy.device)
-            _fp8_dgrad_into(ds8, go, wo, do, rt, 0.0)
-            dq = torch.empty(M, d, dtype=torch.bfloat16, device=dy.device)
-            if fp8.ATTN_BWD_G8 and K.attn_bwd_g8_ok(T, S, hd):
-                # e5m2 dQ (+ amax, bias partials) from the attention backward;
-                # dK / dV stay bf16 (summed over the layers into the batched
-                # cross K|V gradient)
-                dq8 = torch.empty(M, d, dtype=st.gmeta.dtype, device=dy.device)
-                part = K.workspace(f"qcs_q{site}", B * -(-T // 128) * d, dy.device)
-                nparts = K.attn_bwd_g8(q.view(B, T, heads, hd), kv5[:, :, 0], kv5[:, :, 1], o,
-                                       do.view(B, T, heads, hd), aux, dq.view(B, T, heads, hd),
-                                       g5[:, :, 0], g5[:, :, 1], kv_len, scale, False,
-                                       dq8.view(B, T, heads, hd), None, None, st.gmeta.s(gq),
-                                       st.gmeta.a(gq), part, d, 0, 0, 0, skip_bf16=False)
-                _fold_bias_later(rt, part[: nparts * d], nparts, d, bq)
             else:
-                K.attn_bwd(q.view(B, T, heads, hd), kv5[:, :, 0], kv5[:, :, 1], o,
-                           do.view(B, T, heads, hd), aux, dq.view(B, T, heads, hd), g5[:, :, 0],
-                           g5[:, :, 1], kv_len, scale, False)
-                dq8 = _fp8_grad_bias(dq, gq, bq, rt, f"q{site}")
-            _fp8_dgrad_into(dq8, gq, wq, dh.view(M, d), rt, 1.0)
-            rt.wgrad.add_fp8(ds8, st.gmeta.s(go), o8, st.meta.s(os_), wo, bt, rt)
-            rt.wgrad.add_fp8(dq8, st.gmeta.s(gq), x8, st.meta.s(xs), wq, bt, rt)
-            dkv_ret = dkv_all if layer == 0 else None
-            return (dh.view(B, T, d), dkv_ret) + (None,) * 12
+                do = torch.empty(M, d, dtype=torch.bfloat16, device=dy.device)
+                _fp8_dgrad(ds8, go, wo, do, rt, 0.0)
+                dq = torch.empty(M, d, dtype=torch.bfloat16, device=dy.device)
+                if fp8.ATTN_BWD_G8 and K.attn_bwd_g8_ok(T, S, hd):
+                    # e5m2 dQ (+ amax, bias partials) from the attention backward;
+                    # dK / dV stay bf16 (summed over the layers into the batched
+                    # cross K|V gradient)
+                    dq8 = torch.empty(M, d, dtype=st.gmeta.dtype, device=dy.device)
+                    part = K.workspace(f"qcs_q{site}", B * -(-T // 128) * d, dy.device)
+                    nparts = K.attn_bwd_g8(q.view(B, T, heads, hd), kv5[:, :, 0], kv5[:, :, 1], o,
+                                           do.view(B, T, heads, hd), aux, dq.view(B, T, heads, hd),
+                                           g5[:, :, 0], g5[:, :, 1], kv_len, scale, False,
+                                           dq8.view(B, T, heads, hd), None, None, st.gmeta.s(gq),
+                                           st.gmeta.a(gq), part, d, 0, 0, 0, skip_bf16=False)
+                    _fold_bias_later(rt, part[: nparts * d], nparts, d, bq)
+                else:
+                    K.attn_bwd(q.view(B, T, heads, hd), kv5[:, :, 0], kv5[:, :, 1], o,
+                               do.view(B, T, heads, hd), aux, dq.view(B, T, heads, hd), g5[:, :, 0],
+                               g5[:, :, 1], kv_len, scale, False)
+                    dq8 = _fp8_grad_bias(dq, gq, bq, rt, f"q{site}")
+            _lean_bwd_end(lb, dq8, wq, wo, rt)
+            dkv_ret = None
+            if layer == 0:  # (kvh.f8b: the zero-stride placeholder)
+                dkv_ret = dkv_all if dkv_all is not None else torch.zeros(
+                    1, dtype=kv_all.dtype, device=dy.device).expand(kv_all.shape)
+            return (dh.view(B, T, d), dkv_ret) + (None,) * CrossAttnBlockFn.NO_GRAD_ARGS
         dh, ds = _ln_bwd(dy, ctx.ln, gamma, beta, bo, site, rt)
         ds2 = ds.reshape(M, d)
         if dy.is_cuda:
@@ -1051,7 +789,7 @@ class CrossAttnBlockFn(torch.autograd.Function):
         # Only layer 0 hands the (by then complete) shared buffer to autograd;
         # the other layers contribute through the side channel, so no adds.
         dkv_ret = dkv_all if layer == 0 else None
-        return (dx.view(B, T, d), dkv_ret) + (None,) * 12
+        return (dx.view(B, T, d), dkv_ret) + (None,) * CrossAttnBlockFn.NO_GRAD_ARGS
 
 
 # =============================================================================== feed-forward block
@@ -1064,6 +802,7 @@ RELU_BITS = os.environ.get("TDG_RELU_BITS", "1") != "0"
 class FFNBlockFn(torch.autograd.Function):
     """y = LN(x + dropout(Dense(d)(Dense(ff, relu)(x))))."""
 
+    NO_GRAD_ARGS = 8  # forward arguments after x
     @staticmethod
     def forward(ctx, x, w1: Param, b1: Param, w2: Param, b2: Param, gamma: Param, beta: Param,
                 site: int, rt: RunCtx):
@@ -1148,14 +887,14 @@ class FFNBlockFn(torch.autograd.Function):
                     # inputs (FFN1 input x8, hidden h8), token-major
                     x8, h8 = ctx.f8
                     xs, hs = st.ffn_slots[id(w1)]
-                    q = rt.wgrad
+                    q, folds = rt.wgrad, []
                     # (b1's column-sum fold deferred to the wgrad flush with
                     # the LayerNorm folds: one launch instead of one per layer)
                     dpre8 = fp8.gemm_bf8_dgrad(ds8, st.gmeta, gs, w2t8, st.meta, s2t, None,
                                                relu_aux8=h8.view(M, ff), out8_slot=gh,
                                                colsum_out=b1.grad, colsum_beta=bt, w_plain=wp,
-                                               defer=q.reductions)
-                    q.reduced_params.append((rt, b1))
+                                               defer=folds)
+                    q.defer_fold(folds, (b1,), rt)
                     q.add_fp8(ds8.view(M, d), st.gmeta.s(gs), h8.view(M, ff), st.meta.s(hs), w2, bt, rt)
                     q.add_fp8(dpre8.view(M, ff), st.gmeta.s(gh), x8.view(M, d), st.meta.s(xs), w1, bt, rt)
                 else:
@@ -1165,7 +904,7 @@ class FFNBlockFn(torch.autograd.Function):
                     _wgrad(rt, dpre, x2, ff, w1, b1)
                 fp8.gemm_bf8_dgrad(dpre8, st.gmeta, gh, w1t8, st.meta, s1t, dh.view(M, d), beta=1.0,
                                    w_plain=wp)
-                return (dh.view(B, L, d),) + (None,) * 8
+                return (dh.view(B, L, d),) + (None,) * FFNBlockFn.NO_GRAD_ARGS
             # ReLU mask: the forward's bitmap if it wrote one (h is still saved:
             # the W2 weight gradient reads it)
             mask = dict(relu_bits=ctx.hbits) if ctx.hbits is not None else dict(relu_aux=h)
@@ -1176,14 +915,12 @@ class FFNBlockFn(torch.autograd.Function):
             else:
                 dpre = K.linear_dgrad(ds2, w2.compute, d, **mask)
             _wgrad(rt, dpre, x2, ff, w1, b1)
-            dx = _dgrad_res(dpre, w1, ff, dh)
-            return (dx.view(B, L, d),) + (None,) * 8
         else:
             _write_grad(w2, ds2.t() @ h, rt)
             _ready(rt, w2)
             dpre = (ds2 @ w2.master) * (h > 0).to(ds2.dtype)
             _write_grad(w1, dpre.t() @ x2, rt)
             _write_grad(b1, dpre.sum(0), rt)
-        _ready(rt, w1, b1)
+            _ready(rt, w1, b1)  # (GPU: reported by _wgrad / the deferred flush)
         dx = _dgrad_into(dpre, w1, ff, dh)
-        return (dx.view(B, L, d),) + (None,) * 8
+        return (dx.view(B, L, d),) + (None,) * FFNBlockFn.NO_GRAD_ARGS
