@@ -10,6 +10,8 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+import ref_tail as R
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -182,6 +184,18 @@ def test_adam_kernels_apply_clip_factor(n, form):
         _close(out["shadow"], ref, 1e-2, "adam shadow")
         assert out["step"].item() == 11
         assert out["g"].abs().max().item() == 0.0
+        # v = (g * gs * factor)^2 * (1 - beta2) is the buffer that shows the factor (Adam's
+        # first step from zero moments does not depend on the gradient's scale, so p cannot);
+        # p through its update, m and v elementwise against the float64 reference, whose
+        # grad_scale is the f32 product the kernels form from the device's factor
+        gsf = float(torch.tensor(gs, dtype=torch.float32) * out["state"][2].cpu())
+        zero = torch.zeros(n)
+        R.check_adam((out["p"].cpu(), out["m"].cpu(), out["v"].cpu()), c.p, c.g, zero, zero, 10,
+                     R.AdamCfg(grad_scale=gsf), f"{form} gs={gs} clip={clip}")
+        # ... and against the host's factor, which the device's matches to 1e-6 (above):
+        # 2e-6 for its square, on top of the table's f32 tolerance
+        want = (c.g.double() * gs * factor) ** 2 * (1 - R._f32r(0.98))
+        assert bool(((out["v"].cpu().double() - want).abs() <= (2e-6 + R.tol("adam_v")) * want).all())
         if form == "chunks8":
             off, k = W8
             want = F.quantize(out["shadow"][off:off + k], c.meta, c.slot, record=False)

@@ -5,6 +5,7 @@ import math
 import pytest
 import torch
 
+import ref_tail as R
 from tensorflow_distributed_on_gke_amd.ops import kernels as kk
 from tensorflow_distributed_on_gke_amd.ops import philox
 
@@ -426,7 +427,10 @@ def test_embed_fwd_bwd(p):
 @pytest.mark.parametrize("smoothing", [0.0, 0.1])
 def test_xent(smoothing):
     M, V, Vp = 257, 7010, 7040
-    lg = _bf(torch.randn(M, Vp) * 3)
+    lg = torch.randn(M, Vp) * 3
+    lg[0::2, V:] = float("nan")  # what the kernel must not read: the logits GEMM leaves
+    lg[1::2, V:] = 3e38          # these columns of its torch.empty output as they were
+    lg = _bf(lg)
     lab = torch.randint(1, V, (M,))
     lab[::7] = 0
     ntok = torch.zeros(1, device=DEV)
@@ -453,6 +457,15 @@ def test_xent(smoothing):
     _close(lgd[:, :V], x.grad, 2e-2, "dlogits")
     assert lgd[:, V:].float().abs().max().item() == 0.0
     assert acc[2].item() == 1.0
+    # per row and per element against the float64 reference (tests/ref_tail.py)
+    rloss, rcorrect, rn, rd = R.ref_xent(lg[:, :V], lab, 2.0, smoothing)
+    assert ntok.item() == rn
+    R.close_f32(rl.cpu(), rloss, "row_loss", "row_loss", scale=R.row_loss_scale(lg[:, :V]))
+    R.exact(rc.cpu(), rcorrect.float(), "row_correct")
+    R.close_dlogits(lgd.cpu(), rd, V, R.xent_scale(rn, 2.0), "dlogits")
+    sl, sa, sc = R.ref_xent_stats(rl.cpu(), rc.cpu(), rn, 2.0)
+    R.close_f32(so[0:1].cpu(), torch.tensor([sl]), "stats_loss", "stats loss")
+    R.close_accuracy(so[1].item(), sc, rn, "accuracy")
 
 
 # --------------------------------------------------------------------------- adam
@@ -477,6 +490,10 @@ def test_adam_keras_semantics():
     assert step.item() == 11
     assert gd.abs().max().item() == 0.0
     _close(sh, ref, 1e-2, "adam shadow")
+    # the update itself (25x below the tolerance above) and v, elementwise
+    # against the float64 reference (tests/ref_tail.py)
+    R.check_adam((pd.cpu(), md.cpu(), vd.cpu()), p, g, m, v, 10, R.AdamCfg(), "adam")
+    R.exact(sh, pd.to(torch.bfloat16), "adam shadow")
 
 
 # --------------------------------------------------------------------------- grouped launches
