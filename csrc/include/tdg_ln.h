@@ -106,7 +106,11 @@ __device__ __forceinline__ uint32_t keep_bits(uint64_t seed, const long long* ct
 // Forward of one row: h = x + dropout(t) (t = the sublayer output, already
 // loaded; has_t false: h = x), h rounded to bf16 (and saved) so forward and
 // backward see the same h, y = (h - mean) * rstd * gamma + beta. Stores y,
-// hsave, mean/rstd; returns y (f32, pre-rounding) in o. Shared by the
+// hsave, mean/rstd; returns y (f32, pre-rounding) in o. Without hsave
+// (inference, infer/greedy.py _add_ln) nothing reads h again, so mean, rstd
+// and y come from the unrounded f32 h: what the CPU decode path's
+// layer_norm(x + s) computes (tests/test_gpu_norm.py test_ln_fwd holds both
+// arms to their own float64 reference). Shared by the
 // standalone LayerNorm and the GEMM+LayerNorm epilogue so both produce
 // bitwise-identical results.
 template <int D>

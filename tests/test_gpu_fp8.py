@@ -134,7 +134,7 @@ def test_fp8_training_tracks_bf16():
     assert abs(f1 - b1) < 0.1 * b1 + 0.05, finals
 
 
-@pytest.mark.parametrize("D", [128, 512, 1024])
+@pytest.mark.parametrize("D", [128, 256, 512, 1024])
 def test_layernorm_fused_fp8_copy(D):
     from tensorflow_distributed_on_gke_amd.ops import kernels as kk
     meta = F.Fp8Meta(DEV)
@@ -423,7 +423,7 @@ def test_gemm_bf8_dgrad_mask8_colsum(M, N, K, with_c, plain, cfg):
     assert berr < 1e-3, berr
 
 
-@pytest.mark.parametrize("D", [512, 1024])
+@pytest.mark.parametrize("D", [128, 256, 512, 1024])
 @pytest.mark.parametrize("p", [0.0, 0.1])
 def test_ln_bwd_emits_e5m2_ds(D, p):
     """LayerNorm backward with the e5m2 copy of ds (the lean fp8 FFN
