@@ -190,6 +190,13 @@ void colsum_grouped(const std::vector<Tensor>& Xs, const std::vector<Tensor>& ou
             "tdg colsum_grouped");
 }
 
+// (family, BM, BN, depth, splits) of this thread's last GEMM launch
+std::vector<int64_t> gemm_last_plan() {
+  int p[5];
+  tdg_gemm_last_plan(p);
+  return {p[0], p[1], p[2], p[3], p[4]};
+}
+
 }  // namespace
 
 void def_gemm(py::module_& m) {
@@ -202,6 +209,7 @@ void def_gemm(py::module_& m) {
   m.def("gemm_ragged", &gemm_ragged, py::arg("As"), py::arg("Bs"), py::arg("Cs"), py::arg("shapes"),
         py::arg("K"), py::arg("a_kc"), py::arg("b_kc"), py::arg("alpha"), py::arg("beta"),
         py::arg("bias_out") = std::vector<c10::optional<Tensor>>{});
+  m.def("gemm_last_plan", &gemm_last_plan);
   m.def("colsum", &colsum);
   m.def("colsum_grouped", &colsum_grouped);
 }

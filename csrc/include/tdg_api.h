@@ -30,6 +30,10 @@ int tdg_gemm_grouped(const void* const* A, const void* const* B, void* const* C,
 int tdg_gemm_ragged(const void* const* A, const void* const* B, void* const* C, int P,
                     const int* shapes, int K, int a_kc, int b_kc, int out_f32, float alpha,
                     float beta, float* const* bias_out, hipStream_t st);
+// The GEMM launch this thread made last, as its launcher recorded it: family
+// (0 lock-step tiles, 1 256x256 ragged kernel, 2 pipelined kernel), BM, BN,
+// pipeline depth, effective split-K count. family -1: none yet. Host only.
+void tdg_gemm_last_plan(int out[5]);
 void tdg_colsum(const void* X, float* out, float* part, int M, int N, int ld, int rows_per_block,
                 float beta, hipStream_t st);
 int tdg_colsum_grouped(const void* const* X, float* const* out, int G, float* part, int M, int N,

@@ -117,7 +117,17 @@ __global__ __launch_bounds__(256) void reduce_partials_grouped_kernel(ColsumGrou
   }
 }
 
+int* gemm_plan_slot() {
+  static thread_local int plan[5] = {-1, 0, 0, 0, 0};
+  return plan;
+}
+
 }  // namespace tdg
+
+extern "C" void tdg_gemm_last_plan(int out[5]) {
+  const int* p = gemm_plan_slot();
+  for (int i = 0; i < 5; ++i) out[i] = p[i];
+}
 
 // Public launcher. a_kc/b_kc select operand layouts. Returns 0 on success.
 extern "C" int tdg_gemm(const void* A, const void* B, void* C, const float* bias, const void* aux,

@@ -415,8 +415,12 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const R256Args args,
       }
     }
   }
-  const int nrec_a = 2 * (A_KC ? (M - 1) * lda + K : (K - 1) * lda + M);
-  const int nrec_b = 2 * (B_KC ? (N - 1) * ldb + K : (K - 1) * ldb + N);
+  // (MN-contiguous: whole 16-byte chunks of the last K row, which the operand
+  // contract makes readable -- a chunk straddling the end of the records is
+  // dropped by the range check, i.e. row K - 1 of columns 8 * (M / 8).. read
+  // as zero whenever M % 8 != 0)
+  const int nrec_a = 2 * (A_KC ? (M - 1) * lda + K : (K - 1) * lda + ((M + 7) & ~7));
+  const int nrec_b = 2 * (B_KC ? (N - 1) * ldb + K : (K - 1) * ldb + ((N + 7) & ~7));
   const uint32_t kstep_a = A_KC ? BK * 2u : (uint32_t)BK * (uint32_t)lda * 2u;
   const uint32_t kstep_b = B_KC ? BK * 2u : (uint32_t)BK * (uint32_t)ldb * 2u;
   auto issue = [&](const bf16_t* X, int nrec, const uint32_t* offs, uint32_t soff, char* dst) {
@@ -674,6 +678,19 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ ws, void* __restr
 // ============================================================================ host
 using namespace tdg;
 
+namespace tdg {
+// The launch about to be made, for tdg_gemm_last_plan (tdg_api.h): family
+// (0 lock-step gemm_kernel, 1 gemm256_kernel, 2 gemm_pipe_kernel), BM, BN,
+// pipeline depth, effective split count. One thread-local record (gemm.hip),
+// written by the launcher that launches: nothing here predicts a dispatch.
+enum PlanFamily : int { PLAN_LOCK = 0, PLAN_R256 = 1, PLAN_PIPE = 2 };
+int* gemm_plan_slot();
+inline void plan_record(int family, int bm, int bn, int depth, int splits) {
+  int* p = gemm_plan_slot();
+  p[0] = family; p[1] = bm; p[2] = bn; p[3] = depth; p[4] = splits;
+}
+}  // namespace tdg
+
 namespace {
 
 template <int BM, int BN, int WM, int WN, int ST, bool AK, bool BKc, int EPI, bool F32>
@@ -693,6 +710,7 @@ void launch_cfg(const bf16_t* A, const bf16_t* B, void* C, const float* bias, co
     attr_set = true;
   }
   if (splits <= 1 || G > 1) {
+    plan_record(PLAN_LOCK, BM, BN, ST, 1);
     hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, ST, AK, BKc, EPI, F32>), dim3(tiles, G, 1),
                        dim3(WM * WN * 64), lds, st, A, B, C, bias, aux, M, N, K, lda, ldb, ldc,
                        ldaux, alpha, beta, K, 0LL, gr);
@@ -700,6 +718,7 @@ void launch_cfg(const bf16_t* A, const bf16_t* B, void* C, const float* bias, co
     int kps = cdiv(cdiv(K, splits), BK) * BK;
     splits = cdiv(K, kps);
     const long long stride = (long long)M * ldc;
+    plan_record(PLAN_LOCK, BM, BN, ST, splits);
     hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, ST, AK, BKc, EPI_NONE, true>),
                        dim3(tiles, 1, splits), dim3(WM * WN * 64), lds, st, A, B, (void*)ws, bias,
                        aux, M, N, K, lda, ldb, ldc, ldaux, 1.f, 0.f, kps, stride, gr);
@@ -727,8 +746,8 @@ constexpr bool has_256() {
 inline bool r256_offsets_ok(const R256Args& a, bool akc, bool bkc, int K) {
   for (int c = 0; c < a.ncls; ++c) {
     const R256Class& k = a.cls[c];
-    const long long ea = akc ? (long long)(k.M - 1) * k.lda + K : (long long)(K - 1) * k.lda + k.M;
-    const long long eb = bkc ? (long long)(k.N - 1) * k.ldb + K : (long long)(K - 1) * k.ldb + k.N;
+    const long long ea = akc ? (long long)(k.M - 1) * k.lda + K : (long long)(K - 1) * k.lda + ((k.M + 7) & ~7);
+    const long long eb = bkc ? (long long)(k.N - 1) * k.ldb + K : (long long)(K - 1) * k.ldb + ((k.N + 7) & ~7);
     if (ea * 2 >= 0x7fffffffLL || eb * 2 >= 0x7fffffffLL) return false;
   }
   return true;
@@ -749,6 +768,7 @@ int launch_256(const R256Args& args, int tiles, const float* bias, const bf16_t*
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       attr = true;
     }
+    plan_record(PLAN_R256, 256, 256, 2, 1);
     hipLaunchKernelGGL((gemm256_kernel<AK, BKc, EPI, F32>), dim3(tiles), dim3(512), lds, st, args,
                        bias, aux, K, ldaux, alpha, beta);
     return 0;
@@ -781,8 +801,10 @@ bool launch_pipe(const bf16_t* A, const bf16_t* B, void* C, const float* bias, c
   if constexpr (epi_has_bits(EPI) && BN / WN > 64) return false;
   else {
   if (K % PK != 0 || K <= 0) return false;
-  const long long ab = AK ? (long long)(M - 1) * lda + K : (long long)(K - 1) * lda + M;
-  const long long bb = BKc ? (long long)(N - 1) * ldb + K : (long long)(K - 1) * ldb + N;
+  // records of an MN-contiguous operand end on a whole 16-byte chunk (readable by
+  // the operand contract): the range check drops a chunk that straddles the end
+  const long long ab = AK ? (long long)(M - 1) * lda + K : (long long)(K - 1) * lda + ((M + 7) & ~7);
+  const long long bb = BKc ? (long long)(N - 1) * ldb + K : (long long)(K - 1) * ldb + ((N + 7) & ~7);
   if (ab * 2 >= 0x7fffffffLL || bb * 2 >= 0x7fffffffLL) return false;
   if ((!AK && lda % 8) || (!BKc && ldb % 8)) return false;
   constexpr int lds = NS * (BM + BN) * PK * 2;
@@ -793,6 +815,7 @@ bool launch_pipe(const bf16_t* A, const bf16_t* B, void* C, const float* bias, c
     attr = true;
   }
   const int tiles = cdiv(M, BM) * cdiv(N, BN);
+  plan_record(PLAN_PIPE, BM, BN, NS, 1);
   hipLaunchKernelGGL((gemm_pipe_kernel<BM, BN, WM, WN, NS, AK, BKc, EPI, F32>), dim3(tiles),
                      dim3(WM * WN * 64), lds,
                      st, A, B, C, bias, aux, M, N, K, lda, ldb, ldc, ldaux, alpha, beta,
