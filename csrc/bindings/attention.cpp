@@ -59,7 +59,7 @@ void fill_qkv(tdg::AttnArgs& a, const Tensor& q, const Tensor& k, const Tensor& 
   check_rows_aligned(v, kv_align, "attention v");
 }
 // A bf16 [B, L, H, hd] operand shaped like q (L = Lq) or k (L = Lk); 16-byte
-// rows: the kernels store whole 16-byte row chunks (attention.hip store_row16)
+// rows: the kernels store whole 16-byte row chunks (attn_impl.h store_row16)
 void check_like(const Tensor& t, const tdg::AttnArgs& a, int L, const char* n) {
   check_bf16(t, n);
   TORCH_CHECK(t.dim() == 4 && t.stride(3) == 1 && t.size(0) == a.B && t.size(1) == L &&
@@ -321,7 +321,7 @@ void attn_bwd_g8(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor
   check_err(tdg_attn_bwd(&a, 64, stream_of(q)), "tdg attn_bwd_g8");
 }
 
-// fp8 attention backward (attention.hip attn_bwd_f8_kernel): e4m3 q8/k8/v8
+// fp8 attention backward (attn_f8.h attn_bwd_f8_kernel): e4m3 q8/k8/v8
 // (the forward's operands, scales sq/sk/sv), e5m2 do8 (scale sdo), bf16 o,
 // the forward's lse; dS quantised with sds (amax into amaxds). Outputs, each
 // written when given: bf16 dq/dk/dv, e5m2 dq8/dk8/dv8 (scale sg8, amax into

@@ -39,7 +39,7 @@ void tdg_colsum(const void* X, float* out, float* part, int M, int N, int ld, in
 int tdg_colsum_grouped(const void* const* X, float* const* out, int G, float* part, int M, int N,
                        int ld, int rows_per_block, float beta, hipStream_t st);
 
-// ---------------------------------------------------------------- attention.hip
+// ---------------------------------------------------------------- attention.hip (attn_{fwd,bwd,f8,qkv}.h)
 // -1 from tdg_qkv_attn_fwd / tdg_attn_bwd_fdo: shape not covered, nothing launched
 int tdg_attn_fwd(const tdg::AttnArgs* a, int hd, hipStream_t st);
 int tdg_qkv_attn_fwd(const tdg::QkvAttnArgs* qa, hipStream_t st);

@@ -75,7 +75,7 @@ struct AttnArgs {
 };
 
 // Fused self-attention input projection + attention forward
-// (attention.hip qkv_attn_fwd_kernel): a's out / lse / kv_len / o strides /
+// (attn_qkv.h qkv_attn_fwd_kernel): a's out / lse / kv_len / o strides /
 // B / H / Lq / Lk / scale / causal, plus the projection's operands
 struct QkvAttnArgs {
   AttnArgs a;

@@ -4,7 +4,8 @@
 //
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -DTDG_STAMPS -Icsrc/include \
 //         -x hip csrc/lab/attn_lab.cpp -o lab_bin/attn_lab
-#include "../kernels/attention.hip"
+#include "../kernels/attn_fwd.h"
+#include "../kernels/attn_bwd.h"
 #include "lab_common.h"
 
 int main() {

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timing of the fp8 attention backward (attention.hip attn_bwd_f8_kernel)
+"""Timing of the fp8 attention backward (attn_f8.h attn_bwd_f8_kernel)
 against the bf16 backward (dQ + dK/dV pipelined kernels) on config 5's
 attention shape: B 16, H 16, L 512, hd 64 (HIP events, median of rounds).
 

@@ -79,7 +79,7 @@ def precision_map() -> Dict[str, str]:
     }
 
 
-# fp8 attention backward (attention.hip attn_bwd_f8_kernel, sequences of
+# fp8 attention backward (attn_f8.h attn_bwd_f8_kernel, sequences of
 # 129-512 at hd 64): the forward's e4m3 Q/K/V and e4m3 P, e5m2 dO and dS on
 # the fp8 MFMAs, every key of a (batch, head) in one workgroup (P and dS once)
 ATTN_BWD_F8 = os.environ.get("TDG_ATTN_BWD_F8", "1") != "0"
@@ -495,7 +495,7 @@ class Fp8State:
         # LayerNorms whose output is an fp8 GEMM input: they emit the e4m3 copy
         self.ln_slots: Dict[int, int] = {}
         # attention input projections: weight -> activation slot, output slot
-        # (their e4m3 outputs feed the e4m3 attention, attention.hip
+        # (their e4m3 outputs feed the e4m3 attention, attn_f8.h
         # attn_fwd_fp8_kernel, on the sequences it covers)
         self.proj_slots: Dict[int, int] = {}
         self.out_slots: Dict[int, int] = {}

@@ -391,7 +391,7 @@ def attn_fwd(q, k, v, kv_len, scale: float, causal: bool):
 
 
 # self-attention of <= 128 tokens: the Q|K|V projection and the attention
-# forward in one launch (attention.hip qkv_attn_fwd_kernel)
+# forward in one launch (attn_qkv.h qkv_attn_fwd_kernel)
 QKV_ATTN = os.environ.get("TDG_QKV_ATTN", "1") != "0"
 
 
@@ -415,7 +415,7 @@ def qkv_attn_fwd(x2, w, bias, B: int, heads: int, kv_len, scale: float, causal: 
 
 
 def attn_fwd_fp8_ok(Lq: int, Lk: int, hd: int) -> bool:
-    """Shapes the e4m3 attention forward covers (attention.hip
+    """Shapes the e4m3 attention forward covers (attn_f8.h
     attn_fwd_fp8_kernel): hd 64, the long-sequence path."""
     return hd == 64 and Lq > 128
 
@@ -454,7 +454,7 @@ def attn_bwd_fdo(q, k, v, o, dy2, wo, lse, dq, dk, dv, kv_len, scale: float, cau
 
 def attn_bwd_g8_ok(Lq: int, Lk: int, hd: int) -> bool:
     """Shapes whose attention backward can emit e5m2 gradients (the hd-64
-    pipelined kernels, attention.hip attn_emit_g8)."""
+    pipelined kernels, attn_bwd.h attn_emit_g8)."""
     return hd == 64 and (Lq > 128 or Lk > 128)
 
 
@@ -479,7 +479,7 @@ def attn_bwd_g8(q, k, v, o, dout, lse, dq, dk, dv, kv_len, scale: float, causal:
 
 
 def attn_bwd_f8_ok(Lq: int, Lk: int, hd: int) -> bool:
-    """Shapes the fp8 attention backward covers (attention.hip
+    """Shapes the fp8 attention backward covers (attn_f8.h
     attn_bwd_f8_kernel: every key of a (batch, head) in one workgroup)."""
     return hd == 64 and 128 < Lq <= 512 and Lk <= 512
 

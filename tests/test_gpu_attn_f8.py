@@ -1,4 +1,4 @@
-"""fp8 attention backward (attention.hip attn_bwd_f8_kernel): e4m3 Q/K/V/P,
+"""fp8 attention backward (attn_f8.h attn_bwd_f8_kernel): e4m3 Q/K/V/P,
 e5m2 dO/dS on the fp8 MFMAs, checked against fp32 autograd of attention on
 the dequantised operands (the e4m3 Q/K/V the forward ran on and the e5m2 dO
 the kernel reads), plus its e5m2 outputs, amax records and bias-gradient

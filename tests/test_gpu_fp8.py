@@ -169,7 +169,7 @@ def _attn_ref(q, k, v, kv_len, causal, scale):
 @pytest.mark.parametrize("causal,Lq,Lk", [(False, 512, 512), (True, 512, 512), (False, 260, 390),
                                           (False, 200, 70), (True, 300, 300), (True, 700, 700)])
 def test_attention_fwd_fp8(causal, Lq, Lk):
-    """e4m3 attention forward (attention.hip attn_fwd_fp8_kernel) against fp32 attention of the dequantised e4m3 inputs: the error
+    """e4m3 attention forward (attn_f8.h attn_fwd_fp8_kernel) against fp32 attention of the dequantised e4m3 inputs: the error
     left is the e4m3 rounding of P. Ragged key lengths and a kv_len = 0 row
     (non-causal)."""
     from tensorflow_distributed_on_gke_amd.ops import kernels as kk

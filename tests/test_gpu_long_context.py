@@ -7,7 +7,7 @@ and sizes its positional-encoding table for 1000 positions
 part of its workload; SURVEY §5 asks for 512..8k. Covered here:
 
 * bf16 attention forward + backward (the streaming multi-tile kernels:
-  attention.hip attn_fwd_pipe_kernel / attn_bwd_dq_pipe_kernel /
+  attn_fwd.h attn_fwd_pipe_kernel, attn_bwd.h attn_bwd_dq_pipe_kernel /
   attn_bwd_dkdv_pipe_kernel for hd 64, the register-staged kernels for hd 16)
   at Lq = Lk in {1000, 2048, 4096} with padding and look-ahead masks, against
   fp32 autograd of the same attention (computed on the GPU in fp32: the CPU

@@ -1,5 +1,5 @@
 """The fused self-attention input projection + attention forward
-(attention.hip qkv_attn_fwd_kernel: one launch per layer for sequences of
+(attn_qkv.h qkv_attn_fwd_kernel: one launch per layer for sequences of
 <= 128 tokens) against the two-launch path it replaces -- the Q|K|V GEMM
 (linear_fwd) then attn_fwd on its output -- and the attention against a plain
 fp32 PyTorch softmax(Q K^T / sqrt(hd) + mask) V (reference:
