@@ -20,6 +20,7 @@ using c10::optional;
 // they name. module.cpp calls them all.
 void def_gemm(py::module_& m);
 void def_attention(py::module_& m);
+void def_decode(py::module_& m);
 void def_layernorm(py::module_& m);
 void def_embedding(py::module_& m);
 void def_fp8(py::module_& m);

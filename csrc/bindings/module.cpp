@@ -5,6 +5,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "gfx950 (MI355X) HIP kernels for tensorflow_distributed_on_gke_amd";
   def_gemm(m);
   def_attention(m);
+  def_decode(m);
   def_layernorm(m);
   def_embedding(m);
   def_fp8(m);

@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "tdg_attn.h"
+#include "tdg_decode.h"
 
 extern "C" {
 
@@ -48,6 +49,12 @@ int tdg_attn_bwd_fdo(const tdg::AttnArgs* a, hipStream_t st);
 int tdg_attn_probs(const tdg::AttnArgs* a, int hd, float* probs, hipStream_t st);
 int tdg_attn_fwd_fp8(const tdg::AttnArgs* a, int hd, hipStream_t st);
 int tdg_attn_bwd_f8(const tdg::AttnArgs* a, int hd, hipStream_t st);
+
+// ---------------------------------------------------------------- decode.hip
+// -1: hd not 16 / 64 (decode_attn), beam outside [1, 8] or V outside
+// [1, 65536] (beam_topk); nothing launched
+int tdg_decode_attn(const tdg::DecodeAttnArgs* a, int hd, hipStream_t st);
+int tdg_beam_topk(const tdg::BeamTopkArgs* a, hipStream_t st);
 
 // ---------------------------------------------------------------- norm.hip
 // ctr: device RNG step counter (or null); site: dropout site id; y8 / s8 /

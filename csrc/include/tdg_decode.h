@@ -1,0 +1,48 @@
+// Argument blocks of the decoding kernels (decode.hip), host <-> device.
+#pragma once
+#include <stdint.h>
+
+namespace tdg {
+
+// Single-query attention: one query per (row, head), keys reached through an
+// index. All strides are in bf16 elements; every 8-element slice of a row
+// lies on a 16-byte boundary.
+struct DecodeAttnArgs {
+  const uint16_t* q;  // [R, H, hd]
+  uint16_t* out;      // [R, H, hd]
+  uint16_t* k;        // [n_src, Lk, H, hd] (written only by the fused append)
+  uint16_t* v;
+  // fused append (both or neither): [R, H, hd], stored to cache position
+  // kv_len[r] - 1 of row r and used as that key
+  const uint16_t* k_new;
+  const uint16_t* v_new;
+  const int* kv_len;   // [R], keys j < kv_len[r] are used; >= 1
+  const int* anc;      // [R, ld_anc] cache row of key j of row r, or null
+  const int* row_map;  // [R] cache row of every key of row r (anc null), or null = r
+  long long k_sr, k_sk, v_sr, v_sk;  // cache row / key strides
+  int k_sh, v_sh;                    // head strides
+  int q_sr, q_sh, o_sr, o_sh, kn_sr, kn_sh, vn_sr, vn_sh;
+  int ld_anc;
+  int R, H, Lk;
+  int n_src;  // cache rows: anc / row_map entries are clamped into [0, n_src)
+  float scale;
+};
+
+// One beam-search selection step, B sentences x beam hypotheses (rows
+// r = sentence * beam + slot).
+struct BeamTopkArgs {
+  const uint16_t* logits;  // bf16 [R, ldl], the first V columns count
+  const float* score;      // [R]
+  const int* fin;          // [R] 1 = hypothesis has ended
+  float* score_out;        // [R] per new slot, descending
+  int* parent;             // [R] global row the slot continues
+  int* token;              // [R]
+  int* fin_out;            // [R]
+  // ancestry update (both or neither): anc_out[r][:t+1] = anc_in[parent[r]][:t+1],
+  // anc_out[r][t+1] = r
+  const int* anc_in;
+  int* anc_out;
+  int B, beam, V, ldl, end_id, pad_id, ld_anc, t;
+};
+
+}  // namespace tdg

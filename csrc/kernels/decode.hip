@@ -1,0 +1,331 @@
+// Decoding kernels (gfx950): single-query attention over an indexed K/V cache
+// and the beam-search selection step. Used by infer/beam.py.
+//
+// decode_attn: M = 1 per (row, head), so there is no matrix to feed the MFMA
+// units: the kernel is a stream over the keys. One wave per (row, head), four
+// per workgroup, no LDS. hd / 8 lanes share a key (one 16-byte load of K and
+// one of V each), so a wave covers 64 / (hd / 8) keys per pass. Every lane
+// group keeps its own online softmax (running max, sum and f32 accumulator of
+// its keys; P is never rounded); the groups are merged once at the end.
+// Which cache row holds key j of row r comes from the ancestry table
+// (anc[r][j]) or, without one, from row_map[r]: beams never reorder a cache,
+// and the encoder K/V exist once per sentence.
+//
+// beam_topk: one workgroup per sentence. Per live row the f32 logsumexp of the
+// logits, then every thread keeps the best `beam` of the candidates it scans
+// (score[r] + logp[r, v], ordered by value, ties to the lower flat index
+// r_local * V + v) and the workgroup merges the lists with `beam` arg-max
+// rounds. The same launch advances the ancestry table.
+#include "tdg_api.h"
+#include "tdg_common.h"
+
+namespace tdg {
+
+// ---------------------------------------------------------------- decode_attn
+__device__ __forceinline__ void unpack8(const uint4& w, float* f) {
+  const uint32_t u[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    f[2 * i] = __uint_as_float(u[i] << 16);
+    f[2 * i + 1] = __uint_as_float(u[i] & 0xffff0000u);
+  }
+}
+
+template <int HD>
+__global__ __launch_bounds__(256) void decode_attn_kernel(const DecodeAttnArgs a) {
+  constexpr int LPK = HD / 8;    // lanes per key (8 bf16 = 16 bytes each)
+  constexpr int KPW = 64 / LPK;  // keys per wave pass
+  const int lane = threadIdx.x & 63;
+  const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (pair >= a.R * a.H) return;  // whole waves leave
+  const int r = pair / a.H, h = pair - r * a.H;
+  const int g = lane / LPK, e0 = (lane % LPK) * 8;
+  uint16_t* const orow = a.out + (long long)r * a.o_sr + h * a.o_sh + e0;
+  const int n = min(a.kv_len[r], a.Lk);
+  if (n < 1) {  // outside the precondition: defined as zeros, nothing read
+    if (lane < LPK) *reinterpret_cast<uint4*>(orow) = make_uint4(0, 0, 0, 0);
+    return;
+  }
+  float q[8];
+  {
+    const uint4 w = *reinterpret_cast<const uint4*>(a.q + (long long)r * a.q_sr + h * a.q_sh + e0);
+    unpack8(w, q);
+    const float sc = a.scale * 1.44269504088896f;  // softmax in base 2
+#pragma unroll
+    for (int i = 0; i < 8; ++i) q[i] *= sc;
+  }
+  const bool fused = a.k_new != nullptr;
+  const int t = n - 1;
+  int own = r;
+  if (a.anc == nullptr && a.row_map != nullptr) own = a.row_map[r];
+  own = min(max(own, 0), a.n_src - 1);
+  const int* const anc = a.anc ? a.anc + (long long)r * a.ld_anc : nullptr;
+
+  float m = -INFINITY, l = 0.f, acc[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+
+  for (int j0 = 0; j0 < n; j0 += KPW) {
+    const int j = j0 + g;
+    const bool valid = j < n;
+    uint4 kw = make_uint4(0, 0, 0, 0), vw = kw;
+    if (valid) {
+      if (fused && j == t) {
+        // the new key: from the projection's output, and into the cache
+        kw = *reinterpret_cast<const uint4*>(a.k_new + (long long)r * a.kn_sr + h * a.kn_sh + e0);
+        vw = *reinterpret_cast<const uint4*>(a.v_new + (long long)r * a.vn_sr + h * a.vn_sh + e0);
+        *reinterpret_cast<uint4*>(a.k + r * a.k_sr + t * a.k_sk + h * a.k_sh + e0) = kw;
+        *reinterpret_cast<uint4*>(a.v + r * a.v_sr + t * a.v_sk + h * a.v_sh + e0) = vw;
+      } else {
+        int src = own;
+        if (anc) src = min(max(anc[j], 0), a.n_src - 1);
+        kw = *reinterpret_cast<const uint4*>(a.k + src * a.k_sr + j * a.k_sk + h * a.k_sh + e0);
+        vw = *reinterpret_cast<const uint4*>(a.v + src * a.v_sr + j * a.v_sk + h * a.v_sh + e0);
+      }
+    }
+    float kf[8], s = 0.f;
+    unpack8(kw, kf);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s = fmaf(q[i], kf[i], s);
+#pragma unroll
+    for (int o = 1; o < LPK; o <<= 1) s += __shfl_xor(s, o);
+    if (valid) {
+      float vf[8];
+      unpack8(vw, vf);
+      const float mn = fmaxf(m, s);
+      const float alpha = exp2f(m - mn), p = exp2f(s - mn);
+      m = mn;
+      l = l * alpha + p;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc[i] = acc[i] * alpha + p * vf[i];
+    }
+  }
+  // merge the lane groups: rescale to the wave's max, then sum lanes of equal
+  // slice across the groups (m = -inf, a group without keys, scales to 0)
+  const float f = exp2f(m - wave_max(m));
+  l *= f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc[i] *= f;
+#pragma unroll
+  for (int o = LPK; o < 64; o <<= 1) {
+    l += __shfl_xor(l, o);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] += __shfl_xor(acc[i], o);
+  }
+  if (lane < LPK) {
+    const float inv = 1.f / l;
+    uint4 w;
+    w.x = pack2bf(acc[0] * inv, acc[1] * inv);
+    w.y = pack2bf(acc[2] * inv, acc[3] * inv);
+    w.z = pack2bf(acc[4] * inv, acc[5] * inv);
+    w.w = pack2bf(acc[6] * inv, acc[7] * inv);
+    *reinterpret_cast<uint4*>(orow) = w;
+  }
+}
+
+// ---------------------------------------------------------------- beam_topk
+constexpr int NO_CAND = 0x7fffffff;
+
+// candidate order: higher value first, equal values by the lower flat index
+__device__ __forceinline__ bool better(float av, int ai, float bv, int bi) {
+  return av > bv || (av == bv && ai < bi);
+}
+
+__device__ __forceinline__ float block_max(float v, float* red) {
+  const float w = wave_max(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
+  __syncthreads();
+  const float r = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  return r;
+}
+__device__ __forceinline__ float block_sum(float v, float* red) {
+  const float w = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
+  __syncthreads();
+  const float r = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  return r;
+}
+
+template <int BEAM>
+__global__ __launch_bounds__(256) void beam_topk_kernel(const BeamTopkArgs a) {
+  __shared__ float red[4];
+  __shared__ int redi[4];
+  __shared__ int s_parent[BEAM];
+  const int tid = threadIdx.x;
+  const int r0 = blockIdx.x * BEAM;
+  const int V = a.V;
+
+  float lv[BEAM];  // this thread's best candidates, best first
+  int li[BEAM];
+#pragma unroll
+  for (int i = 0; i < BEAM; ++i) {
+    lv[i] = -INFINITY;
+    li[i] = NO_CAND;
+  }
+  auto offer = [&](float cv, int ci) {
+    if (!better(cv, ci, lv[BEAM - 1], li[BEAM - 1])) return;
+#pragma unroll
+    for (int i = 0; i < BEAM; ++i) {
+      if (better(cv, ci, lv[i], li[i])) {
+        const float tv = lv[i];
+        const int ti = li[i];
+        lv[i] = cv;
+        li[i] = ci;
+        cv = tv;
+        ci = ti;
+      }
+    }
+  };
+
+  for (int b = 0; b < BEAM; ++b) {  // every branch below is workgroup-uniform
+    const int r = r0 + b;
+    const float sc = a.score[r];
+    if (!(sc > -INFINITY)) continue;  // a dead slot (or NaN) offers nothing
+    if (a.fin[r]) {                   // ended: itself, once, score unchanged
+      if (tid == 0) offer(sc, b * V + a.pad_id);
+      continue;
+    }
+    const uint16_t* x = a.logits + (long long)r * a.ldl;
+    float mx = -INFINITY;
+    for (int c = tid * 8; c < V; c += 2048) {
+      float f[8];
+      unpack8(*reinterpret_cast<const uint4*>(x + c), f);
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        if (c + i < V) mx = fmaxf(mx, f[i]);
+    }
+    mx = block_max(mx, red);
+    if (!(mx > -INFINITY)) continue;  // no finite logit
+    float sum = 0.f;
+    for (int c = tid * 8; c < V; c += 2048) {
+      float f[8];
+      unpack8(*reinterpret_cast<const uint4*>(x + c), f);
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        if (c + i < V) sum += __expf(f[i] - mx);
+    }
+    const float lse = mx + logf(block_sum(sum, red));
+    for (int c = tid * 8; c < V; c += 2048) {
+      float f[8];
+      unpack8(*reinterpret_cast<const uint4*>(x + c), f);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float cv = sc + (f[i] - lse);
+        if (c + i < V && cv > -INFINITY) offer(cv, b * V + c + i);
+      }
+    }
+  }
+
+  // merge: BEAM rounds of workgroup arg-max over the lists' heads
+  for (int k = 0; k < BEAM; ++k) {
+    float bv = lv[0];
+    int bi = li[0];
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const float ov = __shfl_xor(bv, o);
+      const int oi = __shfl_xor(bi, o);
+      if (better(ov, oi, bv, bi)) {
+        bv = ov;
+        bi = oi;
+      }
+    }
+    if ((tid & 63) == 0) {
+      red[tid >> 6] = bv;
+      redi[tid >> 6] = bi;
+    }
+    __syncthreads();
+    bv = red[0];
+    bi = redi[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w)
+      if (better(red[w], redi[w], bv, bi)) {
+        bv = red[w];
+        bi = redi[w];
+      }
+    __syncthreads();
+    if (bi != NO_CAND && li[0] == bi) {  // the winner's owner moves on
+#pragma unroll
+      for (int i = 0; i + 1 < BEAM; ++i) {
+        lv[i] = lv[i + 1];
+        li[i] = li[i + 1];
+      }
+      lv[BEAM - 1] = -INFINITY;
+      li[BEAM - 1] = NO_CAND;
+    }
+    if (tid == 0) {
+      const int r = r0 + k;
+      if (bi == NO_CAND) {  // fewer candidates than slots: a dead slot
+        a.score_out[r] = -INFINITY;
+        a.parent[r] = r0;
+        a.token[r] = a.pad_id;
+        a.fin_out[r] = 1;
+        s_parent[k] = r0;
+      } else {
+        const int b = bi / V, tok = bi - b * V;
+        a.score_out[r] = bv;
+        a.parent[r] = r0 + b;
+        a.token[r] = tok;
+        a.fin_out[r] = (a.fin[r0 + b] != 0 || tok == a.end_id) ? 1 : 0;
+        s_parent[k] = r0 + b;
+      }
+    }
+  }
+  if (a.anc_out == nullptr) return;
+  __syncthreads();
+  const int w = a.t + 2;
+  for (int i = tid; i < BEAM * w; i += 256) {
+    const int b = i / w, j = i - b * w;
+    a.anc_out[(long long)(r0 + b) * a.ld_anc + j] =
+        j <= a.t ? a.anc_in[(long long)s_parent[b] * a.ld_anc + j] : r0 + b;
+  }
+}
+
+template <int BEAM>
+static void launch_beam_topk(const BeamTopkArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(beam_topk_kernel<BEAM>, dim3(a.B), dim3(256), 0, st, a);
+}
+
+}  // namespace tdg
+
+extern "C" {
+
+// out[r, h, :] = softmax(scale * q[r, h] . K[row(r, j), j, h] for j < kv_len[r]) @ V,
+// row(r, j) = anc[r][j], else row_map[r], else r; with k_new / v_new the new
+// key is stored to cache position kv_len[r] - 1 of row r and used from
+// registers. kv_len[r] >= 1 (a row with none gets zeros). hd 16 or 64.
+int tdg_decode_attn(const tdg::DecodeAttnArgs* a, int hd, hipStream_t st) {
+  if (hd != 16 && hd != 64) return -1;
+  if (a->R <= 0 || a->H <= 0) return 0;
+  const dim3 grid(tdg::cdiv(a->R * a->H, 4)), block(256);
+  if (hd == 64)
+    hipLaunchKernelGGL(tdg::decode_attn_kernel<64>, grid, block, 0, st, *a);
+  else
+    hipLaunchKernelGGL(tdg::decode_attn_kernel<16>, grid, block, 0, st, *a);
+  return 0;
+}
+
+// One beam-search step (tdg_decode.h BeamTopkArgs): per sentence the best
+// `beam` of the candidates (r, v) -> score[r] + log_softmax(logits[r])[v];
+// an ended row offers only (r, pad_id) with its score, a row of score -inf
+// nothing. Slots come out by descending score, ties by the lower flat index;
+// a slot with no candidate left gets score -inf, token pad_id, fin 1, parent
+// = the sentence's first row. ldl % 8 == 0, 16-byte aligned logits.
+int tdg_beam_topk(const tdg::BeamTopkArgs* a, hipStream_t st) {
+  if (a->beam < 1 || a->beam > 8 || a->V < 1 || a->V > 65536) return -1;
+  if (a->B <= 0) return 0;
+  switch (a->beam) {
+    case 1: tdg::launch_beam_topk<1>(*a, st); break;
+    case 2: tdg::launch_beam_topk<2>(*a, st); break;
+    case 3: tdg::launch_beam_topk<3>(*a, st); break;
+    case 4: tdg::launch_beam_topk<4>(*a, st); break;
+    case 5: tdg::launch_beam_topk<5>(*a, st); break;
+    case 6: tdg::launch_beam_topk<6>(*a, st); break;
+    case 7: tdg::launch_beam_topk<7>(*a, st); break;
+    default: tdg::launch_beam_topk<8>(*a, st); break;
+  }
+  return 0;
+}
+
+}  // extern "C"

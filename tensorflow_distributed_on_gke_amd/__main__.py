@@ -1,7 +1,7 @@
 """Command line entry point.
 
     python -m tensorflow_distributed_on_gke_amd train [--config FILE] [--set key=value ...] [--nproc N]
-    python -m tensorflow_distributed_on_gke_amd test  --weights PREFIX [--sentence TEXT ...]
+    python -m tensorflow_distributed_on_gke_amd test  --weights PREFIX [--sentence TEXT ...] [--beam N]
     python -m tensorflow_distributed_on_gke_amd heartbeat --port 3479
 
 `train` is the reference's `python -m distributed_training_transformer`
@@ -11,7 +11,8 @@ the heartbeat barrier and launches one training process per local GPU
 (`--nproc`, default: all visible GPUs); locally it launches `--nproc`
 processes on 127.0.0.1, or runs in-process when started by
 torch.distributed.run (RANK set) or with one process.
-`test` is the reference's test.py + Tester (greedy translation).
+`test` is the reference's test.py + Tester (greedy translation, or beam
+search with --beam N --length-penalty ALPHA).
 """
 from __future__ import annotations
 
@@ -92,7 +93,8 @@ def cmd_test(args) -> int:
     if args.weights:
         bundle.load_weights(model.store, args.weights)
     tester = Tester(tok, model)
-    text, tokens, attn = tester(list(args.sentence), max_length=args.max_length)
+    text, tokens, attn = tester(list(args.sentence), max_length=args.max_length, beam=args.beam,
+                                alpha=args.length_penalty)
     for s, t in zip(args.sentence, text):
         print(f"{s!r} -> {t!r}")
     print("attention maps:", {k: tuple(v.shape) for k, v in attn.items()})
@@ -126,6 +128,9 @@ def main(argv=None) -> int:
     e.add_argument("--weights", default=None, help="weights prefix or directory")
     e.add_argument("--sentence", action="append", default=None)
     e.add_argument("--max-length", type=int, default=20)
+    e.add_argument("--beam", type=int, default=1, help="beam width (1 = greedy, at most 8)")
+    e.add_argument("--length-penalty", type=float, default=0.6,
+                   help="alpha of the beam ranking score / ((5 + len) / 6) ** alpha")
     h = sub.add_parser("heartbeat")
     h.add_argument("--port", type=int, default=3479)
     args = ap.parse_args(argv)

@@ -152,11 +152,21 @@ class Tester:
             out[f"decoder_layer{i + 1}_block2"] = rt.attn_maps[layer.site2]
         return out
 
-    def __call__(self, sentence: Union[str, Sequence[str]], max_length: int = 20, kv_cache: bool = True
+    def __call__(self, sentence: Union[str, Sequence[str]], max_length: int = 20, kv_cache: bool = True,
+                 beam: int = 1, alpha: float = 0.6
                  ) -> Tuple[Union[str, List[str]], list, Dict[str, torch.Tensor]]:
+        """beam > 1: beam search (infer/beam.py) with length penalty `alpha`
+        instead of the greedy argmax; the return value has the same form."""
         single = isinstance(sentence, str)
         src = self.src_tok.tokenize(sentence)
-        out = (self.greedy_cached if kv_cache else self.greedy)(src, max_length).cpu()
+        if beam > 1:
+            from tensorflow_distributed_on_gke_amd.infer.beam import beam_search
+
+            start, end = self.tgt_tok.start_end()
+            out = beam_search(self.model, src, start, end, beam=beam, max_length=max_length,
+                              alpha=alpha)[0].cpu()
+        else:
+            out = (self.greedy_cached if kv_cache else self.greedy)(src, max_length).cpu()
         texts, tokens = [], []
         _, end = self.tgt_tok.start_end()
         for row in out.tolist():

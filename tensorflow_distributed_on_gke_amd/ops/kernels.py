@@ -511,6 +511,104 @@ def attn_probs(q, k, kv_len, scale: float, causal: bool) -> torch.Tensor:
     return probs
 
 
+# ------------------------------------------------------------------ decoding
+def decode_attn(q, k, v, kv_len, scale: float, anc=None, row_map=None, k_new=None, v_new=None):
+    """Single-query attention, one query per (row, head): q [R, H, hd], k / v
+    cache views [rows, Lk, H, hd] (any row / key / head strides) -> [R, H, hd].
+
+    Key j < kv_len[r] (int32 [R], >= 1) of row r is read from cache row
+    anc[r, j] (int32 [R, >= Lk]) when `anc` is given, else from row_map[r]
+    (int32 [R]), else from row r. With k_new / v_new ([R, H, hd]) the new key
+    is first stored to position kv_len[r] - 1 of cache row r (in place) and
+    used as that key. GPU: bf16, hd 16 or 64 (csrc/kernels/decode.hip); CPU:
+    the same in f32 through models.layers._ref_attn_fwd."""
+    R, H, hd = q.shape
+    if q.is_cuda:
+        out = torch.empty(R, H, hd, dtype=torch.bfloat16, device=q.device)
+        C().decode_attn(q, k, v, out, kv_len, scale, anc, row_map, k_new, v_new)
+        return out
+    from tensorflow_distributed_on_gke_amd.models.layers import _ref_attn_fwd
+
+    n = kv_len.long().clamp(max=k.shape[1])
+    rows = torch.arange(R)
+    if k_new is not None:
+        k[rows, n - 1] = k_new.to(k.dtype)
+        v[rows, n - 1] = v_new.to(v.dtype)
+    L = int(n.max())
+    keys = torch.arange(L)
+    if anc is not None:
+        src = anc[:, :L].long()
+        if k_new is not None:  # the new key is row r's own, whatever anc says
+            src = src.clone()
+            src[rows, n - 1] = rows
+    else:
+        src = (row_map.long() if row_map is not None else rows).view(R, 1).expand(R, L)
+    src = src.clamp(0, k.shape[0] - 1)
+    used = (keys.view(1, L) < n.view(R, 1)).view(R, L, 1, 1)
+    zero = torch.zeros((), dtype=torch.float32)
+    kg = torch.where(used, k[src, keys.view(1, L)].float(), zero)  # unused keys are never read
+    vg = torch.where(used, v[src, keys.view(1, L)].float(), zero)
+    out = _ref_attn_fwd(q.float().view(R, 1, H, hd), kg, vg, n.to(torch.int32), False, scale)[0]
+    return out.view(R, H, hd).to(q.dtype)
+
+
+def beam_topk(logits, V: int, score, fin, beam: int, end_id: int, pad_id: int, anc=None, t: int = 0,
+              anc_out=None):
+    """One beam-search selection step for rows r = sentence * beam + slot.
+
+    logits [R, >= V] (only the first V columns count), score f32 [R], fin
+    int32 [R]. Candidate (r, v) scores score[r] + log_softmax(logits[r])[v] in
+    f32; an ended row offers only (r, pad_id) with its score unchanged, a row
+    of score -inf nothing. Per sentence the best `beam` candidates, ties to
+    the lower flat index slot * V + v, by descending score; a slot left
+    without a candidate gets score -inf, token pad_id, fin 1 and the
+    sentence's first row as parent. Returns (score f32, parent int32 (global
+    row), token int32, fin int32, anc'), anc' being the ancestry table
+    advanced from `anc` (int32 [R, > t + 1]): anc'[r, :t+1] =
+    anc[parent[r], :t+1], anc'[r, t+1] = r (None without `anc`), written into
+    `anc_out` (a second table, never `anc` itself) when given; later columns
+    are not defined. 1 <= beam <= 8, V <= 65536."""
+    R = logits.shape[0]
+    if not 1 <= beam <= 8 or not 1 <= V <= 65536:
+        raise RuntimeError(f"beam_topk: beam {beam} outside [1, 8] or V {V} outside [1, 65536]")
+    dev = logits.device
+    if logits.is_cuda:
+        score_out = torch.empty(R, dtype=torch.float32, device=dev)
+        parent, token, fin_out = (torch.empty(R, dtype=torch.int32, device=dev) for _ in range(3))
+        if anc is not None and anc_out is None:
+            anc_out = torch.zeros_like(anc)
+        C().beam_topk(logits, V, score, fin, beam, end_id, pad_id, score_out, parent, token, fin_out,
+                      anc, anc_out, t)
+        return score_out, parent, token, fin_out, anc_out
+    B = R // beam
+    x = logits[:, :V].float()
+    logp = x - torch.logsumexp(x, dim=-1, keepdim=True)
+    cand = score.float().view(R, 1) + logp
+    ended = fin.view(R, 1) != 0
+    only_pad = torch.full_like(cand, float("-inf"))
+    only_pad[:, pad_id] = score.float()
+    cand = torch.where(ended, only_pad, cand)
+    cand = torch.where(torch.isnan(cand) | ~(score.float() > float("-inf")).view(R, 1),
+                       torch.full_like(cand, float("-inf")), cand)
+    flat = cand.view(B, beam * V)
+    order = torch.sort(-flat, dim=-1, stable=True).indices[:, :beam]  # ties: lower flat index
+    val = torch.gather(flat, 1, order)
+    dead = ~(val > float("-inf"))
+    base = (torch.arange(B) * beam).view(B, 1)
+    parent = torch.where(dead, base.expand(B, beam), base + order // V)
+    token = torch.where(dead, torch.full_like(order, pad_id), order % V)
+    fin_out = dead | (fin.view(R)[parent.view(R)].view(B, beam) != 0) | (token == end_id)
+    score_out = torch.where(dead, torch.full_like(val, float("-inf")), val)
+    parent = parent.reshape(R).to(torch.int32)
+    if anc is not None:
+        if anc_out is None:
+            anc_out = torch.zeros_like(anc)
+        anc_out[:, : t + 1] = anc[parent.long(), : t + 1]
+        anc_out[:, t + 1] = torch.arange(R, dtype=anc.dtype)
+    return (score_out.reshape(R), parent, token.reshape(R).to(torch.int32),
+            fin_out.reshape(R).to(torch.int32), anc_out)
+
+
 # ------------------------------------------------------------------ layernorm
 def ln_fwd(x, s, gamma, beta, p, seed, ctr, site, eps=1e-6, save=True, y8=None, s8=None,
            amax8=None, kbits=None):
