@@ -127,7 +127,7 @@ int tdg_to_bf16(const float* p, void* o, long long n, hipStream_t st);
 int tdg_transpose_grouped(const void* const* src, void* const* dst, int G, int R, int C,
                           hipStream_t st);
 
-// ---------------------------------------------------------------- fp8.hip
+// ------------------------------------ fp8_gemm.hip, fp8_wgrad.hip, fp8_quant.hip
 // afmt / cfmt / fmt: 0 e4m3, 1 e5m2; amax: a 2048-word slot (or slot table)
 int tdg_gemm_fp8(const void* A, const void* B, void* C, const float* bias, const float* sa,
                  const float* sb, void* C8, const float* sc8, unsigned* amax, int M, int N, int K,
@@ -138,7 +138,9 @@ int tdg_gemm_fp8(const void* A, const void* B, void* C, const float* bias, const
 int tdg_wgrad_fp8(const void* const* A, const void* const* B, float* const* C,
                   const float* const* sa, const float* const* sb, int P, const int* shapes, int T,
                   float beta, hipStream_t st);
-int tdg_fp8_set_persist(int on);  // 1 on / 0 off / -1 query; returns the previous state
+// on: bit mask over the F8_EPI_* epilogue ids (fp8_epi.h) that take the
+// persistent 128x128 kernel (0 off, 0xff all); < 0 queries. Returns the old mask.
+int tdg_fp8_set_persist(int on);
 int tdg_fp8_quant(const void* x, void* y8, long long n, const float* scale, unsigned* amax,
                   int fmt, hipStream_t st);
 int tdg_fp8_quant_multi(const void* const* x, void* const* y, const long long* n, const int* slot,

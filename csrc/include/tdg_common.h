@@ -444,3 +444,14 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 }  // namespace tdg
+
+// Host: raise Kernel's dynamic LDS limit on first use (the kernels that take
+// more than the default 64 KiB)
+template <auto Kernel>
+void big_lds(int bytes = 160 * 1024) {
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    attr = true;
+  }
+}

@@ -1,6 +1,7 @@
-// Shared pieces of the MFMA GEMM kernels (gemm.hip, fp8.hip): LDS tile
-// image layout (XOR-swizzled), the LDS-DMA operand stager, counted waits and
-// MFMA fragment reads.
+// Shared pieces of the MFMA GEMM kernels (gemm.hip; the fp8 GEMMs keep their
+// 8-bit form of the stager in fp8_impl.h): LDS tile image layout
+// (XOR-swizzled), the LDS-DMA operand stager, counted waits and MFMA fragment
+// reads.
 #pragma once
 #include "tdg_common.h"
 

@@ -436,16 +436,7 @@ __device__ __forceinline__ float row_delta(const short8_t (&of)[KS], const short
 
 }  // namespace tdg
 
-// Host: raise Kernel's dynamic LDS limit on first use (the kernels that take
-// more than the default 64 KiB)
-template <auto Kernel>
-void big_lds(int bytes = 160 * 1024) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    attr = true;
-  }
-}
+// (big_lds<Kernel>(): tdg_common.h)
 
 #define TDG_HD_CASES(F, ...)           \
   switch (hd) {                        \

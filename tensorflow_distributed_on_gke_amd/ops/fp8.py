@@ -1,6 +1,6 @@
 """FP8 training path (BASELINE config 5: "Transformer-big seq_len=512 fp8 MFMA
 attention+FFN"): e4m3 / e5m2 operands on gfx950's block-scaled MFMA
-(`v_mfma_scale_f32_*_f8f6f4`, csrc/kernels/fp8.hip) with delayed
+(`v_mfma_scale_f32_*_f8f6f4`, csrc/kernels/fp8_gemm.hip) with delayed
 per-tensor scaling.
 
 Every fp8 operand has a slot in a device-resident `Fp8Meta` (e4m3 for
@@ -36,6 +36,12 @@ E4M3_MAX = 448.0
 E5M2_MAX = 57344.0
 AMAX_WORDS = 64 * 32  # per slot (csrc/include/tdg_common.h AMAX_WORDS)
 _CANDS = (0, 1, 2, 3, 4, 5, 8, 9, 10)
+# gemm_fp8's `epi`: an epilogue id plus flags (csrc/kernels/fp8_epi.h F8_EPI_*,
+# F8_EPI_CDEQ, F8_B_NCONTIG, F8_CS_DEFER)
+EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_DRELU = 0, 1, 2, 3
+EPI_CDEQ = 16  # y = dequant(y8)
+EPI_B_NCONTIG = 32  # B is [K][N] (a plain weight as its dgrad's operand)
+EPI_CS_DEFER = 64  # the column-sum partials stay unfolded
 # FFN weight gradients in fp8 (wgrad_fp8) when the step runs the fp8 backward
 WGRAD_FP8 = True
 # attention projections in fp8 too (Fp8State(backward=True)): output
@@ -196,7 +202,7 @@ def gemm_fp8(a8, b8, bias, meta: Fp8Meta, ia: int, ib: int, relu: bool = False,
              out8_slot: Optional[int] = None, cfg: Optional[int] = None, c_deq: bool = False,
              want_y: bool = True) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
     """y[M,N] = dequant(a8[M,K] @ b8[N,K]^T) + bias (relu), bf16, on the
-    block-scaled e4m3 MFMA (csrc/kernels/fp8.hip); with out8_slot also
+    block-scaled e4m3 MFMA (csrc/kernels/fp8_gemm.hip); with out8_slot also
     y8 = e4m3(y * scale[out8_slot]) (amax recorded). c_deq (needs out8_slot):
     y = y8 / scale instead, the exact values the e4m3 consumer of y8 sees
     (scales are powers of two), so a backward reading y is consistent with
@@ -209,7 +215,7 @@ def gemm_fp8(a8, b8, bias, meta: Fp8Meta, ia: int, ib: int, relu: bool = False,
         raise ValueError("gemm_fp8: c_deq needs out8_slot")
     if not want_y and (y8 is None or c_deq):
         raise ValueError("gemm_fp8: want_y=False needs out8_slot and no c_deq")
-    epi = (2 if relu else (1 if bias is not None else 0)) | (16 if c_deq else 0)
+    epi = (EPI_BIAS_RELU if relu else (EPI_BIAS if bias is not None else EPI_NONE)) | (EPI_CDEQ if c_deq else 0)
     y = torch.empty(M, N, dtype=torch.bfloat16, device=a8.device) if want_y else None
 
     def run(c):
@@ -264,9 +270,9 @@ def gemm_bf8_dgrad(g8, gmeta: Fp8Meta, ig: int, w8, wmeta: Fp8Meta, iw: int,
         # per output)
         key = "fp8_colsum" if defer is None else f"fp8_colsum_{colsum_out.data_ptr()}"
         ws = K.workspace(key, nparts * N, g8.device)
-    epi = (3 if aux is not None else 0) | (32 if w_plain else 0)
+    epi = (EPI_DRELU if aux is not None else EPI_NONE) | (EPI_B_NCONTIG if w_plain else 0)
     if colsum_out is not None and defer is not None:
-        epi |= 64
+        epi |= EPI_CS_DEFER
     C().gemm_fp8(g8, w8, out, None, gmeta.s(ig), wmeta.s(iw), o8,
                  gmeta.s(out8_slot) if o8 is not None else None,
                  gmeta.a(out8_slot) if o8 is not None else None,
@@ -283,7 +289,7 @@ def wgrad_fp8(dy8s, sas, x8s, sbs, dws, beta: float = 0.0) -> None:
     """dws[i][M,N] (f32, =|+= beta) = dequant(dy8s[i][T,M]^T @ x8s[i][T,N]):
     weight gradients from the e5m2 gradient and the e4m3 activation copies
     the step already holds (token-major, read through the transposing LDS
-    path: csrc/kernels/fp8.hip wgrad_fp8_kernel). sas / sbs: the one-element
+    path: csrc/kernels/fp8_wgrad.hip wgrad_fp8_kernel). sas / sbs: the one-element
     scale tensors of each operand. One launch per token count T, shape
     classes adjacent, at most 64 problems in 8 shape classes per launch (the
     kernel's argument block)."""
@@ -318,7 +324,7 @@ def wgrad_fp8_ok(T: int, M: int, N: int) -> bool:
 
 
 def choose_fp8(M: int, N: int, Kd: int) -> int:
-    """fp8 tile config without a timed search (csrc/kernels/fp8.hip table):
+    """fp8 tile config without a timed search (csrc/kernels/fp8_gemm.hip table):
     128x128 on 4 waves whenever that fills the CUs -- it beat 256x128 / 8
     waves on every Transformer-big forward shape, 3-14 % (qkv 42.7 vs 47.0 us,
     xkv6 160.6 vs 186.6; profiles/r3/fp8_gemm_sweep.jsonl)."""

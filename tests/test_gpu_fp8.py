@@ -385,6 +385,32 @@ def test_fp8_ffn_wgrad_matches_bf16_path(monkeypatch):
         assert rel < 0.1, (n, rel)
 
 
+def _dgrad_mask8_case(M, N, K):
+    """Operands, scale slots and the fp32 reference of the ReLU-backward dgrad
+    with the mask from the e4m3 hidden (h8 != 0)."""
+    torch.manual_seed(4)
+    wm, gm = F.Fp8Meta(DEV), F.Fp8Meta(DEV, fmt=1)
+    iw, ig, io, ih = wm.slot("w"), gm.slot("g"), gm.slot("o"), wm.slot("h")
+    wm.scale[iw], gm.scale[ig], gm.scale[io], wm.scale[ih] = 512.0, 2.0 ** 20, 2.0 ** 10, 8.0
+    g = (torch.randn(M, K, device=DEV) * 1e-3).bfloat16()
+    w = (torch.randn(N, K, device=DEV) * 0.05).bfloat16()
+    h = torch.relu(torch.randn(M, N, device=DEV)).bfloat16()
+    h8 = F.quantize(h, wm, ih).view(M, N)
+    g8, w8 = F.quantize(g, gm, ig), F.quantize(w, wm, iw)
+    ref = ((g8.float() / 2.0 ** 20) @ (w8.float() / 512.0).t()) * (h8.float() != 0)
+    return wm, gm, iw, ig, io, g8, w8, h8, ref
+
+
+def _check_dgrad_mask8_out(o8, out, ref):
+    # (the kernel quantises the bf16-rounded value; compare values: masked
+    # elements are +0 from the kernel, -0 in ref * 0)
+    o8ref = (ref.bfloat16().float() * 2.0 ** 10).clamp(-57344, 57344).to(torch.float8_e5m2)
+    assert (o8.float() == o8ref.float()).float().mean().item() > 0.995
+    if out is not None:
+        err = (out.float() - ref).abs().max().item() / (ref.abs().max().item() + 1e-12)
+        assert err < 1e-2, err
+
+
 @pytest.mark.parametrize("M,N,K", [(512, 384, 256), (333, 1000, 512), (1024, 4096, 1024)])
 @pytest.mark.parametrize("with_c", [True, False])
 @pytest.mark.parametrize("plain", [False, True])
@@ -396,31 +422,28 @@ def test_gemm_bf8_dgrad_mask8_colsum(M, N, K, with_c, plain, cfg):
     epilogue partials."""
     if plain and N % 16:
         pytest.skip("the N-contiguous weight path needs N % 16 == 0")
-    torch.manual_seed(4)
-    wm, gm = F.Fp8Meta(DEV), F.Fp8Meta(DEV, fmt=1)
-    iw, ig, io, ih = wm.slot("w"), gm.slot("g"), gm.slot("o"), wm.slot("h")
-    wm.scale[iw], gm.scale[ig], gm.scale[io], wm.scale[ih] = 512.0, 2.0 ** 20, 2.0 ** 10, 8.0
-    g = (torch.randn(M, K, device=DEV) * 1e-3).bfloat16()
-    w = (torch.randn(N, K, device=DEV) * 0.05).bfloat16()
-    h = torch.relu(torch.randn(M, N, device=DEV)).bfloat16()
-    h8 = F.quantize(h, wm, ih).view(M, N)
-    g8, w8 = F.quantize(g, gm, ig), F.quantize(w, wm, iw)
-    ref = ((g8.float() / 2.0 ** 20) @ (w8.float() / 512.0).t()) * (h8.float() != 0)
+    wm, gm, iw, ig, io, g8, w8, h8, ref = _dgrad_mask8_case(M, N, K)
     out = torch.empty(M, N, device=DEV).bfloat16() if with_c else None
     bsum = torch.randn(N, device=DEV)
     bref = bsum + ref.bfloat16().float().sum(0)
     o8 = F.gemm_bf8_dgrad(g8, gm, ig, w8.t().contiguous() if plain else w8, wm, iw, out,
                           relu_aux8=h8, out8_slot=io, colsum_out=bsum, colsum_beta=1.0, w_plain=plain,
                           cfg=cfg)
-    # (the kernel quantises the bf16-rounded value; compare values: masked
-    # elements are +0 from the kernel, -0 in ref * 0)
-    o8ref = (ref.bfloat16().float() * 2.0 ** 10).clamp(-57344, 57344).to(torch.float8_e5m2)
-    assert (o8.float() == o8ref.float()).float().mean().item() > 0.995
-    if with_c:
-        err = (out.float() - ref).abs().max().item() / (ref.abs().max().item() + 1e-12)
-        assert err < 1e-2, err
+    _check_dgrad_mask8_out(o8, out, ref)
     berr = (bsum - bref).abs().max().item() / (bref.abs().max().item() + 1e-12)
     assert berr < 1e-3, berr
+
+
+@pytest.mark.parametrize("M,N,K", [(300, 520, 256), (64, 64, 128)])
+def test_gemm_bf8_dgrad_mask8_cfg9(M, N, K):
+    """The 256x256 one-wave-per-SIMD tile (cfg 9) with the 8-bit ReLU mask
+    (gemm_fp8_w1_kernel<F8_EPI_DRELU8>): partial tiles in both directions and
+    two K steps, and a single partial tile with one K step; bf16 output and
+    e5m2 copy held to the reference and thresholds of the colsum test."""
+    wm, gm, iw, ig, io, g8, w8, h8, ref = _dgrad_mask8_case(M, N, K)
+    out = torch.empty(M, N, device=DEV).bfloat16()
+    o8 = F.gemm_bf8_dgrad(g8, gm, ig, w8, wm, iw, out, relu_aux8=h8, out8_slot=io, cfg=9)
+    _check_dgrad_mask8_out(o8, out, ref)
 
 
 @pytest.mark.parametrize("D", [128, 256, 512, 1024])
@@ -731,7 +754,7 @@ def test_adam_chunk_kernel_matches_grid_adam_and_quant_multi():
 @pytest.mark.parametrize("M,N,Kd", [(8192, 4096, 1024), (3000, 3072, 384), (8192, 1536, 256),
                                      (8192, 1040, 256), (1100, 1280, 256)])
 def test_fp8_gemm_persistent_matches_oneshot(M, N, Kd):
-    """The persistent 128x128 fp8 GEMM (fp8.hip gemm_fp8_pk_kernel: tiles
+    """The persistent 128x128 fp8 GEMM (fp8_gemm_tile.h gemm_fp8_pk_kernel: tiles
     walked by 2 workgroups per CU, the next tile's first K step in flight
     under the epilogue) writes bitwise what the one-shot grid writes: forward
     bias (+ReLU, e4m3 copy, amax) and the e5m2 dgrads (plain-weight transposing
@@ -783,3 +806,68 @@ def test_fp8_gemm_persistent_matches_oneshot(M, N, Kd):
     for i, (r, g) in enumerate(zip(ref, got)):
         assert torch.equal(r, g), (i, (r.float() - g.float()).abs().max().item())
     assert torch.equal(am_ref, am_got)
+
+
+@pytest.mark.parametrize("fmt", [0, 1])
+def test_quantize_exact_on_representable_values(fmt):
+    """Every finite value of the format (but -0), halved, at scale 2: the
+    conversion is exact, so quantize returns each byte pattern itself -- 253
+    elements for e4m3 and 247 for e5m2, so the 8-wide path and the scalar
+    tail (5 / 7 elements) both run -- and the amax is max / 2."""
+    meta = F.Fp8Meta(DEV, fmt=fmt)
+    i = meta.slot("x")
+    meta.scale[i] = 2.0
+    codes = torch.arange(256, dtype=torch.uint8, device=DEV)
+    vals = codes.view(meta.dtype).float()
+    codes = codes[torch.isfinite(vals) & (codes != 0x80)]
+    assert codes.numel() == (247 if fmt else 253)
+    x = (codes.view(meta.dtype).float() / 2).bfloat16()
+    x8 = F.quantize(x, meta, i)
+    assert torch.equal(x8.view(torch.uint8), codes)
+    assert meta.amax_values()[i].item() == (28672.0 if fmt else 224.0)
+
+
+def _reject_cases():
+    """(id, keyword overrides of _reject_call) the fp8 GEMM refuses on the host."""
+    cases = [("a_e4m3_c_e5m2", dict(afmt=0, cfmt=1)),
+             ("a_e5m2_c_e4m3", dict(afmt=1, cfmt=0)),
+             ("a_e4m3_relu_backward", dict(epi=3, aux=True)),
+             ("ncontig_b_with_bias", dict(afmt=1, cfmt=1, epi=32 | 1, bias=True)),
+             ("colsum_cfg9", dict(afmt=1, cfmt=1, cfg=9, colsum=True)),
+             ("defer_without_colsum", dict(afmt=1, cfmt=1, epi=64)),
+             ("cdeq_without_c8", dict(epi=16)),
+             ("k64", dict(K=64))]
+    for cfg in (0, 9, 10):
+        for e in (1, 2):
+            cases.append((f"e5m2_epi{e}_cfg{cfg}", dict(afmt=1, cfmt=1, epi=e, bias=True, cfg=cfg)))
+    return cases
+
+
+@pytest.mark.parametrize("kw", [c[1] for c in _reject_cases()], ids=[c[0] for c in _reject_cases()])
+def test_gemm_fp8_rejects_unsupported(kw):
+    """Combinations the fp8 GEMM dispatcher has no kernel for raise, and no
+    output is written (M = N = K = 128 unless the case says otherwise)."""
+    M = N = 128
+    K = kw.get("K", 128)
+    afmt, cfmt, epi, cfg = kw.get("afmt", 0), kw.get("cfmt", 0), kw.get("epi", 0), kw.get("cfg", 0)
+    a8 = torch.zeros(M, K, device=DEV).to(F.BF8 if afmt else F.FP8)
+    b8 = torch.zeros(N, K, device=DEV).to(F.FP8)  # (N = K: either layout of B)
+    one = torch.ones(1, device=DEV)
+    out = torch.full((M, N), 7.0, dtype=torch.bfloat16, device=DEV)
+    bias = torch.zeros(N, device=DEV) if kw.get("bias") else None
+    aux = torch.ones(M, N, dtype=torch.bfloat16, device=DEV) if kw.get("aux") else None
+    cs = torch.full((N,), 7.0, device=DEV) if kw.get("colsum") else None
+    ws = torch.full((2 * N,), 7.0, device=DEV) if kw.get("colsum") else None
+    c8 = amax = None
+    if not epi & 16:  # (that case is "C = dequant(C8) without C8")
+        c8 = torch.full((M, N), 0x55, dtype=torch.uint8, device=DEV).view(F.BF8 if cfmt else F.FP8)
+        amax = torch.zeros(F.AMAX_WORDS, dtype=torch.int32, device=DEV)
+    with pytest.raises(RuntimeError):
+        C().gemm_fp8(a8, b8, out, bias, one, one, c8, one if c8 is not None else None, amax, M, N, K,
+                     K, K, N, N, epi, cfg, afmt, cfmt, aux, N if aux is not None else 0, 0.0,
+                     colsum_out=cs, ws=ws)
+    torch.cuda.synchronize()
+    for t in (out, cs, ws):
+        assert t is None or bool((t == 7.0).all())
+    if c8 is not None:
+        assert bool((c8.view(torch.uint8) == 0x55).all()) and not bool(amax.any())
