@@ -1,5 +1,8 @@
 // Decoding bindings: single-query attention over an indexed K/V cache and the
-// beam-search selection step (decode.hip).
+// beam-search selection and sampling steps (decode.hip).
+#include <algorithm>
+#include <cmath>
+
 #include "common.h"
 
 namespace {
@@ -143,6 +146,53 @@ void beam_topk(const Tensor& logits, int64_t V, const Tensor& score, const Tenso
   check_err(tdg_beam_topk(&a, stream_of(logits)), "tdg beam_topk");
 }
 
+void sample_token(const Tensor& logits, int64_t V, const Tensor& score, const Tensor& fin,
+                  int64_t end_id, int64_t pad_id, double temperature, int64_t top_k, double top_p,
+                  int64_t seed, int64_t step, const optional<Tensor>& row_id,
+                  const Tensor& score_out, const Tensor& token, const Tensor& fin_out) {
+  TORCH_CHECK(V >= 1 && V <= 65536, "sample_token: V must be in [1, 65536], got ", V);
+  TORCH_CHECK(std::isfinite(temperature) && temperature > 0 && (float)temperature > 0.f,
+              "sample_token: temperature must be finite and > 0, got ", temperature);
+  TORCH_CHECK(top_p > 0 && top_p <= 1 && (float)top_p > 0.f,
+              "sample_token: top_p must be in (0, 1], got ", top_p);
+  TORCH_CHECK(top_k >= 0, "sample_token: top_k must be >= 0, got ", top_k);
+  check_bf16(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.size(1) >= V,
+              "logits must be [R, >= V], rows contiguous");
+  const int64_t R = logits.size(0), ldl = logits.stride(0);
+  TORCH_CHECK(R < (1LL << 31) && ldl < (1LL << 31), "sample_token: logits too large");
+  TORCH_CHECK(ldl % 8 == 0 && ldl >= round8(V),
+              "sample_token: logits row stride must be a multiple of 8");
+  check_aligned(logits, 16, "logits");
+  check_extent(logits, R, ldl, round8(V), "logits");
+  TORCH_CHECK(pad_id >= 0 && pad_id < V && end_id >= 0 && end_id < V, "sample_token: pad / end id");
+  check_f32(score, "score");
+  check_f32(score_out, "score_out");
+  TORCH_CHECK(score.numel() == R && score.is_contiguous() && score_out.numel() == R &&
+                  score_out.is_contiguous(),
+              "score / score_out must be f32 [R]");
+  tdg::SampleArgs a{};
+  a.logits = (const uint16_t*)logits.data_ptr();
+  a.score = score.data_ptr<float>();
+  a.score_out = score_out.data_ptr<float>();
+  a.fin = i32_rows(fin, R, "fin");
+  a.row_id = row_id.has_value() ? i32_rows(*row_id, R, "row_id") : nullptr;
+  a.token = (int*)i32_rows(token, R, "token");
+  a.fin_out = (int*)i32_rows(fin_out, R, "fin_out");
+  a.seed = (unsigned long long)seed;
+  a.step = (unsigned long long)step;
+  a.temperature = (float)temperature;
+  a.top_p = (float)top_p;
+  a.top_k = (int)std::min<int64_t>(top_k, 1 << 30);  // beyond V: off
+  a.R = (int)R;
+  a.V = (int)V;
+  a.ldl = (int)ldl;
+  a.end_id = (int)end_id;
+  a.pad_id = (int)pad_id;
+  c10::DeviceGuard g(logits.device());
+  check_err(tdg_sample_token(&a, stream_of(logits)), "tdg sample_token");
+}
+
 }  // namespace
 
 void def_decode(py::module_& m) {
@@ -155,4 +205,8 @@ void def_decode(py::module_& m) {
         py::arg("beam"), py::arg("end_id"), py::arg("pad_id"), py::arg("score_out"),
         py::arg("parent"), py::arg("token"), py::arg("fin_out"), py::arg("anc_in") = py::none(),
         py::arg("anc_out") = py::none(), py::arg("t") = 0);
+  m.def("sample_token", &sample_token, py::arg("logits"), py::arg("V"), py::arg("score"),
+        py::arg("fin"), py::arg("end_id"), py::arg("pad_id"), py::arg("temperature"),
+        py::arg("top_k"), py::arg("top_p"), py::arg("seed"), py::arg("step"), py::arg("row_id"),
+        py::arg("score_out"), py::arg("token"), py::arg("fin_out"));
 }

@@ -45,4 +45,21 @@ struct BeamTopkArgs {
   int B, beam, V, ldl, end_id, pad_id, ld_anc, t;
 };
 
+// One sampling step (temperature, then top-k, then top-p, then a Gumbel-max
+// draw), one row per hypothesis. Row r draws from the Philox stream of
+// (seed, step, row_id[r]), wherever it sits in the batch.
+struct SampleArgs {
+  const uint16_t* logits;  // bf16 [R, ldl], the first V columns count
+  const float* score;      // [R] running sum of model log-probabilities
+  const int* fin;          // [R] 1 = row has ended
+  const int* row_id;       // [R] identity in the random stream, or null = r
+  float* score_out;        // [R]
+  int* token;              // [R]
+  int* fin_out;            // [R]
+  unsigned long long seed, step;
+  float temperature, top_p;  // T > 0; 0 < top_p <= 1 (1 = off)
+  int top_k;                 // 0 = off
+  int R, V, ldl, end_id, pad_id;
+};
+
 }  // namespace tdg

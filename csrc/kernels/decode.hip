@@ -1,5 +1,6 @@
 // Decoding kernels (gfx950): single-query attention over an indexed K/V cache
-// and the beam-search selection step. Used by infer/beam.py.
+// the beam-search selection step and the sampling step. Used by infer/beam.py
+// and infer/sample.py.
 //
 // decode_attn: M = 1 per (row, head), so there is no matrix to feed the MFMA
 // units: the kernel is a stream over the keys. One wave per (row, head), four
@@ -16,6 +17,13 @@
 // (score[r] + logp[r, v], ordered by value, ties to the lower flat index
 // r_local * V + v) and the workgroup merges the lists with `beam` arg-max
 // rounds. The same launch advances the ancestry table.
+//
+// sample_token: one workgroup per row. The thresholds of top-k and top-p are
+// found by bisection on the 16-bit order-preserving key of a bf16 value (16
+// passes each of a workgroup-wide count or mass of {key >= mid}; a row of up
+// to 8192 columns stays in registers, a longer one, at most 128 KiB, is
+// re-read from L2), the draw is a Gumbel-max over the kept set: no sort, no
+// prefix sums, every reduction in a fixed order.
 #include "tdg_api.h"
 #include "tdg_common.h"
 
@@ -287,6 +295,201 @@ static void launch_beam_topk(const BeamTopkArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(beam_topk_kernel<BEAM>, dim3(a.B), dim3(256), 0, st, a);
 }
 
+// ---------------------------------------------------------------- sample_token
+// The order-preserving 16-bit key of a bf16 logit: a > b <=> okey(a) > okey(b)
+// for finite values (-0 counts as +0). -inf and NaN get 0, below every kept
+// value: the smallest finite bf16 has key KEY_MIN.
+constexpr uint32_t KEY_MIN = 0x0080u;
+__device__ __forceinline__ uint32_t okey(float f) {
+  if (!(f > -INFINITY)) return 0u;
+  uint32_t b = __float_as_uint(f) >> 16;
+  if (b == 0x8000u) b = 0u;
+  return (b & 0x8000u) ? (~b & 0xffffu) : (b | 0x8000u);
+}
+
+// This thread's columns of a row: 8 at c = 8 tid + 2048 j. NCH > 0: the row
+// has at most NCH such chunks and is read once, into registers; NCH == 0: a row
+// of any length, re-read (from L2) by every pass.
+template <int NCH>
+struct RowRegs {
+  uint4 w[NCH > 0 ? NCH : 1];
+  __device__ __forceinline__ void load(const uint16_t* x, int V) {
+    if constexpr (NCH > 0) {
+#pragma unroll
+      for (int j = 0; j < NCH; ++j) {
+        const int c = threadIdx.x * 8 + j * 2048;
+        w[j] = c < V ? *reinterpret_cast<const uint4*>(x + c) : make_uint4(0, 0, 0, 0);
+      }
+    }
+  }
+  // g(c, e, j): the values e[0..8) of columns c .. c + 7, chunk j (0 if NCH == 0)
+  template <class G>
+  __device__ __forceinline__ void chunks(const uint16_t* x, int V, G g) const {
+    if constexpr (NCH > 0) {
+#pragma unroll
+      for (int j = 0; j < NCH; ++j) {
+        const int c = threadIdx.x * 8 + j * 2048;
+        if (c < V) {
+          float e[8];
+          unpack8(w[j], e);
+          g(c, e, j);
+        }
+      }
+    } else {
+      for (int c = threadIdx.x * 8; c < V; c += 2048) {
+        float e[8];
+        unpack8(*reinterpret_cast<const uint4*>(x + c), e);
+        g(c, e, 0);
+      }
+    }
+  }
+  // f(x[v], slot) for the columns v < V, ascending; slot = 8 j + i names the
+  // column among this thread's (NCH > 0)
+  template <class F>
+  __device__ __forceinline__ void scan(const uint16_t* x, int V, F f) const {
+    chunks(x, V, [&](int c, const float* e, int j) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        if (c + i < V) f(e[i], 8 * j + i);
+    });
+  }
+};
+
+template <int NCH>
+__global__ __launch_bounds__(256) void sample_token_kernel(const SampleArgs a) {
+  __shared__ float red[4];
+  __shared__ int redi[4];
+  const int tid = threadIdx.x, r = blockIdx.x, V = a.V;
+  const float sc = a.score[r];
+  auto put = [&](int tok, float s, int fin) {
+    if (tid == 0) {
+      a.token[r] = tok;
+      a.score_out[r] = s;
+      a.fin_out[r] = fin;
+    }
+  };
+  // every branch below is workgroup-uniform
+  if (a.fin[r]) return put(a.pad_id, sc, 1);
+  const uint16_t* x = a.logits + (long long)r * a.ldl;
+  RowRegs<NCH> row;
+  row.load(x, V);
+  float mx = -INFINITY, cnt = 0.f;
+  row.scan(x, V, [&](float f, int) {
+    if (f > -INFINITY) {
+      mx = fmaxf(mx, f);
+      cnt += 1.f;
+    }
+  });
+  mx = block_max(mx, red);
+  if (!(sc > -INFINITY) || !(mx > -INFINITY)) return put(a.pad_id, -INFINITY, 1);
+  const int nfin = (int)block_sum(cnt, red);  // counts are exact in f32
+  float sum = 0.f;
+  row.scan(x, V, [&](float f, int) {
+    if (f > -INFINITY) sum += __expf(f - mx);
+  });
+  const float lse = mx + logf(block_sum(sum, red));
+
+  // tau_k: the largest key t with |{key >= t}| >= top_k, a bit per pass
+  uint32_t tk = KEY_MIN;
+  if (a.top_k > 0 && a.top_k < nfin) {
+    const float need = (float)a.top_k;
+    uint32_t t = 0;
+    for (int bit = 15; bit >= 0; --bit) {
+      const uint32_t cand = t | (1u << bit);
+      float c = 0.f;
+      row.scan(x, V, [&](float f, int) { c += okey(f) >= cand ? 1.f : 0.f; });
+      if (block_sum(c, red) >= need) t = cand;
+    }
+    tk = t;
+  }
+  // tau_p: the largest key t whose mass inside K reaches top_p of K's. While
+  // cand <= tk a pass sums the very set of the total, in the same order. A row
+  // in registers keeps its weights there too (0 outside K).
+  const float T = a.temperature;
+  uint32_t ts = tk;
+  if (a.top_p < 1.f) {
+    float wt[NCH > 0 ? 8 * NCH : 1];
+    if constexpr (NCH > 0)
+      row.scan(x, V, [&](float f, int slot) { wt[slot] = okey(f) >= tk ? expf((f - mx) / T) : 0.f; });
+    auto mass = [&](uint32_t lo) {  // of {key >= lo}, lo >= tk
+      float m = 0.f;
+      row.scan(x, V, [&](float f, int slot) {
+        if (okey(f) >= lo) {
+          if constexpr (NCH > 0)
+            m += wt[slot];
+          else
+            m += expf((f - mx) / T);
+        }
+      });
+      return block_sum(m, red);
+    };
+    const float need = a.top_p * mass(tk);
+    uint32_t t = 0;
+    for (int bit = 15; bit >= 0; --bit) {
+      const uint32_t cand = t | (1u << bit);
+      if (mass(max(cand, tk)) >= need) t = cand;
+    }
+    ts = max(t, tk);
+  }
+
+  // Gumbel-max over S = {key >= ts}: one Philox call per four columns
+  const uint32_t rid = a.row_id ? (uint32_t)a.row_id[r] : (uint32_t)r;
+  float bv = -INFINITY;
+  int bi = NO_CAND;
+  row.chunks(x, V, [&](int c, const float* e, int) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      bool any = false;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) any |= c + 4 * h + i < V && okey(e[4 * h + i]) >= ts;
+      if (!any) continue;
+      uint32_t w[4];
+      Philox::gen(a.seed, a.step, ((uint64_t)rid << 32) | (uint32_t)((c >> 2) + h), w);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int v = c + 4 * h + i;
+        const float f = e[4 * h + i];
+        if (v < V && okey(f) >= ts) {
+          const float u = ((float)(w[i] >> 9) + 0.5f) * 0x1p-23f;  // exact, in (0, 1)
+          const float key = f / T - logf(-logf(u));
+          if (better(key, v, bv, bi)) {
+            bv = key;
+            bi = v;
+          }
+        }
+      }
+    }
+  });
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float ov = __shfl_xor(bv, o);
+    const int oi = __shfl_xor(bi, o);
+    if (better(ov, oi, bv, bi)) {
+      bv = ov;
+      bi = oi;
+    }
+  }
+  if ((tid & 63) == 0) {
+    red[tid >> 6] = bv;
+    redi[tid >> 6] = bi;
+  }
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int w = 1; w < 4; ++w)
+      if (better(red[w], redi[w], bv, bi)) {
+        bv = red[w];
+        bi = redi[w];
+      }
+    if (bi == NO_CAND) {  // no comparable key (NaN logits or temperature): a dead row
+      put(a.pad_id, -INFINITY, 1);
+    } else {
+      const float xt = __uint_as_float((uint32_t)x[bi] << 16);
+      put(bi, sc + (xt - lse), bi == a.end_id ? 1 : 0);
+    }
+  }
+}
+
 }  // namespace tdg
 
 extern "C" {
@@ -325,6 +528,26 @@ int tdg_beam_topk(const tdg::BeamTopkArgs* a, hipStream_t st) {
     case 7: tdg::launch_beam_topk<7>(*a, st); break;
     default: tdg::launch_beam_topk<8>(*a, st); break;
   }
+  return 0;
+}
+
+// One sampling step (tdg_decode.h SampleArgs), a workgroup per row: keep the
+// top_k largest logits (ties at the threshold all kept), of those the smallest
+// top set whose softmax(x / T) mass reaches top_p, and draw by Gumbel-max with
+// uniforms from Philox(seed, step, (row_id, v / 4)). score += the unfiltered
+// log-softmax of the drawn token at T = 1. An ended row gives pad_id, its
+// score and fin 1; a row of score -inf / NaN or without a finite logit
+// pad_id, -inf, fin 1. ldl % 8 == 0, 16-byte aligned logits.
+int tdg_sample_token(const tdg::SampleArgs* a, hipStream_t st) {
+  if (a->V < 1 || a->V > 65536) return -1;
+  if (a->R <= 0) return 0;
+  const dim3 grid(a->R), block(256);
+  if (a->V <= 2048)  // the row in registers: 1 or 4 chunks of 8 columns per thread
+    hipLaunchKernelGGL(tdg::sample_token_kernel<1>, grid, block, 0, st, *a);
+  else if (a->V <= 8192)
+    hipLaunchKernelGGL(tdg::sample_token_kernel<4>, grid, block, 0, st, *a);
+  else
+    hipLaunchKernelGGL(tdg::sample_token_kernel<0>, grid, block, 0, st, *a);
   return 0;
 }
 

@@ -8,7 +8,8 @@ every run decodes all 64 tokens. After a warm-up of each, the three variants
 run interleaved in one process; reported per variant: the median over the
 repeats of generated tokens / s (B * 64 tokens per run, whatever the beam) and
 the spread (min .. max), with every repeat's time. --kernels adds the per-launch times of the attention
-and selection kernels of one step at mid length. Prints one JSON line.
+and selection kernels of one step at mid length (beam_topk, and sample_token on the same rows: plain
+and with top-k and top-p, which add a 16-pass bisection each). Prints one JSON line.
 """
 import argparse
 import json
@@ -76,6 +77,10 @@ def kernel_times(cfg, dev):
             qkv[:, 0], kv[:, :, 0], kv[:, :, 1], slen, 0.125, row_map=rmap))
         o["beam_topk_us"] = _launch_us(lambda: K.beam_topk(lg, 7010, score, fin, beam, END, 0, anc=anc,
                                                            t=t, anc_out=torch.empty_like(anc)))
+        for name, kw in (("sample_token_us", dict()),
+                         ("sample_token_topk_topp_us", dict(temperature=0.8, top_k=40, top_p=0.9))):
+            o[name] = _launch_us(lambda: K.sample_token(lg, 7010, score, fin, END, 0, seed=1, step=t,
+                                                        row_id=rows, **kw))
         if beam == 1:
             q4 = qkv.view(R, 1, 3, H, hd)
 

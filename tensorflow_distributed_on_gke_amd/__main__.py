@@ -2,6 +2,7 @@
 
     python -m tensorflow_distributed_on_gke_amd train [--config FILE] [--set key=value ...] [--nproc N]
     python -m tensorflow_distributed_on_gke_amd test  --weights PREFIX [--sentence TEXT ...] [--beam N]
+            [--sample N --temperature T --top-k K --top-p P --seed S] [--input FILE --output FILE [--batch N]]
     python -m tensorflow_distributed_on_gke_amd heartbeat --port 3479
 
 `train` is the reference's `python -m distributed_training_transformer`
@@ -12,7 +13,9 @@ the heartbeat barrier and launches one training process per local GPU
 processes on 127.0.0.1, or runs in-process when started by
 torch.distributed.run (RANK set) or with one process.
 `test` is the reference's test.py + Tester (greedy translation, or beam
-search with --beam N --length-penalty ALPHA).
+search with --beam N --length-penalty ALPHA, or --sample N translations drawn
+per sentence); with --input / --output it translates a file, one sentence per
+line, to source<TAB>hypothesis<TAB>score lines.
 """
 from __future__ import annotations
 
@@ -93,10 +96,24 @@ def cmd_test(args) -> int:
     if args.weights:
         bundle.load_weights(model.store, args.weights)
     tester = Tester(tok, model)
-    text, tokens, attn = tester(list(args.sentence), max_length=args.max_length, beam=args.beam,
-                                alpha=args.length_penalty)
+    mode = dict(beam=args.beam, alpha=args.length_penalty, sample=args.sample,
+                temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
+    if args.input:
+        # file mode: source<TAB>hypothesis<TAB>score, input order, `sample` lines per source
+        with open(args.input, encoding="utf-8") as f:
+            lines = [line.rstrip("\n") for line in f]
+        flat = lambda t: t.replace("\t", " ").replace("\n", " ").replace("\r", " ")
+        hyps = tester.translate_lines(lines, batch=args.batch, max_length=args.max_length, **mode)
+        with open(args.output, "w", encoding="utf-8") as f:
+            for s, hs in zip(lines, hyps):
+                for h, sc in hs:
+                    f.write(f"{flat(s)}\t{flat(h)}\t{sc:.6f}\n")
+        print(f"{len(lines)} lines -> {args.output}")
+        return 0
+    text, tokens, attn = tester(list(args.sentence), max_length=args.max_length, **mode)
     for s, t in zip(args.sentence, text):
-        print(f"{s!r} -> {t!r}")
+        for h in (t if args.sample > 0 else [t]):
+            print(f"{s!r} -> {h!r}")
     print("attention maps:", {k: tuple(v.shape) for k, v in attn.items()})
     return 0
 
@@ -131,10 +148,27 @@ def main(argv=None) -> int:
     e.add_argument("--beam", type=int, default=1, help="beam width (1 = greedy, at most 8)")
     e.add_argument("--length-penalty", type=float, default=0.6,
                    help="alpha of the beam ranking score / ((5 + len) / 6) ** alpha")
+    e.add_argument("--sample", type=int, default=0, metavar="N",
+                   help="draw N translations per sentence instead (not with --beam)")
+    e.add_argument("--temperature", type=float, default=1.0)
+    e.add_argument("--top-k", type=int, default=0, help="keep the K most likely tokens (0 = all)")
+    e.add_argument("--top-p", type=float, default=1.0, help="keep the top nucleus of this mass (1 = all)")
+    e.add_argument("--seed", type=int, default=0, help="seed of the sampling stream")
+    e.add_argument("--input", default=None, metavar="FILE", help="one source sentence per line")
+    e.add_argument("--output", default=None, metavar="FILE",
+                   help="source<TAB>hypothesis<TAB>score lines, in input order")
+    e.add_argument("--batch", type=int, default=32, help="sentences per batch of --input")
     h = sub.add_parser("heartbeat")
     h.add_argument("--port", type=int, default=3479)
     args = ap.parse_args(argv)
-    if args.cmd == "test" and not args.sentence:
+    if args.cmd == "test":
+        if (args.input is None) != (args.output is None) or (args.input and args.sentence):
+            ap.error("test: --input and --output go together, without --sentence")
+        if args.beam > 1 and args.sample > 0:
+            ap.error("test: --beam and --sample exclude each other")
+        if args.batch < 1 or args.sample < 0:
+            ap.error("test: --batch must be at least 1 and --sample at least 0")
+    if args.cmd == "test" and not args.sentence and not args.input:
         args.sentence = ["muitas pessoas vieram à estação."]  # reference test.py:9
     return {"train": cmd_train, "test": cmd_test, "heartbeat": cmd_heartbeat}[args.cmd](args)
 

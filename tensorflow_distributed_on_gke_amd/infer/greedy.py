@@ -152,30 +152,97 @@ class Tester:
             out[f"decoder_layer{i + 1}_block2"] = rt.attn_maps[layer.site2]
         return out
 
-    def __call__(self, sentence: Union[str, Sequence[str]], max_length: int = 20, kv_cache: bool = True,
-                 beam: int = 1, alpha: float = 0.6
-                 ) -> Tuple[Union[str, List[str]], list, Dict[str, torch.Tensor]]:
-        """beam > 1: beam search (infer/beam.py) with length penalty `alpha`
-        instead of the greedy argmax; the return value has the same form."""
-        single = isinstance(sentence, str)
-        src = self.src_tok.tokenize(sentence)
+    def decode(self, src: torch.Tensor, max_length: int = 20, kv_cache: bool = True, beam: int = 1,
+               alpha: float = 0.6, sample: int = 0, temperature: float = 1.0, top_k: int = 0,
+               top_p: float = 1.0, seed: int = 0, row_id0: int = 0
+               ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """src int64 [B, S] -> (tokens int64 [B, n, 1 + len] on the CPU, scores
+        f32 [B, n] or None): greedy (n = 1, no scores), beam search (beam > 1:
+        n = 1, the best hypothesis) or `sample` draws per sentence."""
+        if sample < 0:
+            raise ValueError(f"sample must be >= 0, got {sample}")
+        if sample > 0 and beam > 1:
+            raise ValueError("beam > 1 and sample > 0 exclude each other")
+        start, end = self.tgt_tok.start_end()
+        if sample > 0:
+            from tensorflow_distributed_on_gke_amd.infer.sample import sample_search
+
+            tokens, scores = sample_search(self.model, src, start, end, n=sample, max_length=max_length,
+                                           temperature=temperature, top_k=top_k, top_p=top_p,
+                                           seed=seed, row_id0=row_id0)
+            return tokens.cpu(), scores.cpu()
         if beam > 1:
             from tensorflow_distributed_on_gke_amd.infer.beam import beam_search
 
-            start, end = self.tgt_tok.start_end()
-            out = beam_search(self.model, src, start, end, beam=beam, max_length=max_length,
-                              alpha=alpha)[0].cpu()
-        else:
-            out = (self.greedy_cached if kv_cache else self.greedy)(src, max_length).cpu()
-        texts, tokens = [], []
+            tokens, scores = beam_search(self.model, src, start, end, beam=beam, max_length=max_length,
+                                         alpha=alpha)[:2]
+            return tokens.cpu().unsqueeze(1), scores.cpu().unsqueeze(1)
+        out = (self.greedy_cached if kv_cache else self.greedy)(src, max_length).cpu()
+        return out.unsqueeze(1), None
+
+    @torch.no_grad()
+    def score(self, src: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
+        """Teacher-forced f32 log-probability [B] of tokens int64 [B, 1 + len]
+        ([START] first): the sum over the generated tokens up to and including
+        the first [END]."""
         _, end = self.tgt_tok.start_end()
-        for row in out.tolist():
-            if end in row:
-                row = row[: row.index(end) + 1]
-            row = [t for t in row if t != PAD_ID]
-            texts.append(self.tgt_tok.detokenize(row))
-            tokens.append(self.tgt_tok.lookup(row))
-        attn = self.attention_weights(src, out[:, :-1])
+        tokens = tokens.to(self.model.device)
+        lp = torch.log_softmax(self.model.logits(src.to(self.model.device), tokens[:, :-1]), dim=-1)
+        tok_lp = lp.gather(2, tokens[:, 1:].unsqueeze(-1)).squeeze(-1)
+        after_end = (tokens[:, 1:] == end).long().cumsum(dim=1) - (tokens[:, 1:] == end).long() > 0
+        return tok_lp.masked_fill(after_end, 0.0).sum(dim=1).cpu()
+
+    def translate_lines(self, lines: Sequence[str], batch: int = 32, max_length: int = 20, **mode
+                        ) -> List[List[Tuple[str, float]]]:
+        """Per line, in input order, its (hypothesis, score) list: one entry
+        (greedy, beam) or `sample` entries. Lines are decoded `batch` at a
+        time in order of source length, so that a batch pads little; `mode`
+        are the decoding arguments of `decode`. In sample mode line i's rows
+        have the identities i * sample .. in the random stream, whichever
+        batch the line falls into."""
+        n = max(1, mode.get("sample", 0))
+        lens = [int((self.src_tok.tokenize(s) != PAD_ID).sum()) for s in lines]
+        order = sorted(range(len(lines)), key=lambda i: (lens[i], i))
+        out: List[List[Tuple[str, float]]] = [[] for _ in lines]
+        for b0 in range(0, len(order), batch):
+            idx = order[b0:b0 + batch]
+            src = self.src_tok.tokenize([lines[i] for i in idx])
+            kw = dict(mode, row_id0=[i * n for i in idx]) if mode.get("sample", 0) > 0 else mode
+            tokens, scores = self.decode(src, max_length, **kw)
+            if scores is None:
+                scores = self.score(src, tokens[:, 0]).view(-1, 1)
+            for j, i in enumerate(idx):
+                out[i] = [(self._text(row)[0], float(scores[j, k]))
+                          for k, row in enumerate(tokens[j].tolist())]
+        return out
+
+    def _text(self, row: List[int]):
+        """One decoded row -> (text, token names), cut after [END], PAD dropped."""
+        _, end = self.tgt_tok.start_end()
+        if end in row:
+            row = row[: row.index(end) + 1]
+        row = [t for t in row if t != PAD_ID]
+        return self.tgt_tok.detokenize(row), self.tgt_tok.lookup(row)
+
+    def __call__(self, sentence: Union[str, Sequence[str]], max_length: int = 20, kv_cache: bool = True,
+                 beam: int = 1, alpha: float = 0.6, sample: int = 0, temperature: float = 1.0,
+                 top_k: int = 0, top_p: float = 1.0, seed: int = 0
+                 ) -> Tuple[Union[str, List[str]], list, Dict[str, torch.Tensor]]:
+        """beam > 1: beam search (infer/beam.py) with length penalty `alpha`
+        instead of the greedy argmax; the return value has the same form.
+        sample > 0: `sample` translations per sentence drawn with temperature,
+        top-k and top-p (infer/sample.py); texts and tokens are then a list per
+        sentence, the attention maps those of every sentence's first sample."""
+        single = isinstance(sentence, str)
+        src = self.src_tok.tokenize(sentence)
+        out, _ = self.decode(src, max_length, kv_cache=kv_cache, beam=beam, alpha=alpha, sample=sample,
+                             temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+        texts, tokens = [], []
+        for rows in out.tolist():
+            pairs = [self._text(row) for row in rows]
+            texts.append([p[0] for p in pairs] if sample > 0 else pairs[0][0])
+            tokens.append([p[1] for p in pairs] if sample > 0 else pairs[0][1])
+        attn = self.attention_weights(src, out[:, 0, :-1])
         if single:
             return texts[0], tokens[0], attn
         return texts, tokens, attn

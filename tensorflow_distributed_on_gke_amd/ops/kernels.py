@@ -609,6 +609,92 @@ def beam_topk(logits, V: int, score, fin, beam: int, end_id: int, pad_id: int, a
             fin_out.reshape(R).to(torch.int32), anc_out)
 
 
+def sample_uniforms(seed: int, step: int, row_id, V: int) -> torch.Tensor:
+    """f64 [R, V]: the uniforms of sample_token, exactly. u[r, v] = ((w >> 9) +
+    0.5) * 2**-23 with w = word v & 3 of Philox(seed, offset=step, idx =
+    row_id[r] << 32 | v >> 2); 23 bits, so the value is exact in f32 too."""
+    from tensorflow_distributed_on_gke_amd.ops import philox
+
+    row_id = row_id.to(torch.int64).cpu()
+    R, G = row_id.numel(), (V + 3) // 4
+    idx = (row_id.view(R, 1) << 32) | torch.arange(G, dtype=torch.int64).view(1, G)
+    words = torch.stack(philox.philox4x32(seed, step, idx), dim=2).view(R, 4 * G)[:, :V]
+    return ((words >> 9).double() + 0.5) * 2.0 ** -23
+
+
+def sample_token(logits, V: int, score, fin, end_id: int, pad_id: int, temperature: float = 1.0,
+                 top_k: int = 0, top_p: float = 1.0, seed: int = 0, step: int = 0, row_id=None):
+    """One sampling step per row: temperature, then top-k, then top-p, then a
+    Gumbel-max draw. Returns (score f32, token int32, fin int32).
+
+    logits [R, >= V] (only the first V columns count; finite or -inf), score
+    f32 [R] (running sum of log-probabilities), fin int32 [R], row_id int32 [R]
+    (the row's identity in the random stream; None = its index).
+    K = {v: x_v >= the top_k-th largest logit} (ties all kept; all finite
+    logits with top_k = 0 or beyond their number); S = {v in K: x_v >= t}, t
+    the largest value whose mass sum_{v in K, x_v >= t} exp((x_v - max x) / T)
+    reaches top_p of K's (top_p = 1: S = K). token = argmax over S of x_v / T -
+    log(-log u_v), ties to the lower v, u as in `sample_uniforms`: a draw from
+    softmax(x / T) restricted to S, the same on the CPU and the GPU wherever
+    the two best keys are not within rounding. score += log_softmax(x)[token]
+    (T = 1, unfiltered: what beam_topk accumulates), fin = token == end_id. An
+    ended row: pad_id, score unchanged, fin 1; a row of score -inf / NaN or
+    without a finite logit: pad_id, -inf, fin 1. GPU: csrc/kernels/decode.hip;
+    CPU: the same definition in f32."""
+    R = logits.shape[0]
+    if not 1 <= V <= 65536:
+        raise RuntimeError(f"sample_token: V {V} outside [1, 65536]")
+    if not (0.0 < temperature < float("inf")) or not 0.0 < top_p <= 1.0 or top_k < 0:
+        raise RuntimeError(f"sample_token: temperature {temperature} must be finite and > 0, "
+                           f"top_p {top_p} in (0, 1], top_k {top_k} >= 0")
+    if not (0 <= pad_id < V and 0 <= end_id < V):
+        raise RuntimeError("sample_token: pad / end id outside [0, V)")
+    dev = logits.device
+    seed, step = seed & (2 ** 64 - 1), step & (2 ** 64 - 1)
+    if logits.is_cuda:
+        score_out = torch.empty(R, dtype=torch.float32, device=dev)
+        token, fin_out = (torch.empty(R, dtype=torch.int32, device=dev) for _ in range(2))
+        s64 = lambda x: x - 2 ** 64 if x >= 2 ** 63 else x  # the same 64 bits, signed
+        C().sample_token(logits, V, score, fin, end_id, pad_id, temperature, top_k, top_p, s64(seed),
+                         s64(step), row_id, score_out, token, fin_out)
+        return score_out, token, fin_out
+    ninf = float("-inf")
+    x = logits[:, :V].float()
+    score = score.float()
+    valid = x > ninf
+    nfin = valid.sum(dim=1)
+    ended = fin.view(R) != 0
+    dead = ~ended & (~(score > ninf) | (nfin == 0))
+    xs = torch.sort(torch.where(valid, x, torch.full_like(x, ninf)), dim=1, descending=True).values
+    kth = torch.full_like(nfin, top_k - 1) if top_k > 0 else nfin - 1
+    kth = torch.where(kth < nfin, kth, nfin - 1).clamp(min=0)
+    tau = xs.gather(1, kth.view(R, 1))
+    keep = valid & (x >= tau)
+    T = torch.tensor(temperature, dtype=torch.float32)
+    if top_p < 1.0:
+        mx = torch.where(nfin > 0, xs[:, 0], torch.zeros(R)).view(R, 1)
+        ws = torch.where((xs > ninf) & (xs >= tau), torch.exp((xs - mx) / T), torch.zeros(()))
+        cum = torch.cumsum(ws, dim=1)
+        # mass of {x >= xs[j]}: the running sum where xs[j]'s run of equal values ends
+        last = torch.ones_like(xs, dtype=torch.bool)
+        last[:, :-1] = xs[:, :-1] != xs[:, 1:]
+        ends = torch.where(last, cum, torch.full_like(cum, float("inf")))
+        mass = torch.flip(torch.cummin(torch.flip(ends, [1]), dim=1).values, [1])
+        ok = mass >= torch.tensor(top_p, dtype=torch.float32) * cum[:, -1:]
+        first = ok.to(torch.int32).argmax(dim=1)
+        keep &= x >= xs.gather(1, first.view(R, 1))
+    rid = torch.arange(R) if row_id is None else row_id
+    u = sample_uniforms(seed, step, rid, V).float()
+    key = torch.where(keep, x / T - torch.log(-torch.log(u)), torch.full_like(x, ninf))
+    token = key.argmax(dim=1)  # the first of equal maxima
+    lse = torch.logsumexp(torch.where(valid, x, torch.full_like(x, ninf)), dim=1)
+    out = score + (x.gather(1, token.view(R, 1)).view(R) - lse)
+    off = ended | dead
+    token = torch.where(off, torch.full_like(token, pad_id), token)
+    out = torch.where(ended, score, torch.where(dead, torch.full_like(out, ninf), out))
+    return out, token.to(torch.int32), (off | (token == end_id)).to(torch.int32)
+
+
 # ------------------------------------------------------------------ layernorm
 def ln_fwd(x, s, gamma, beta, p, seed, ctr, site, eps=1e-6, save=True, y8=None, s8=None,
            amax8=None, kbits=None):
