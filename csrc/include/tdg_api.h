@@ -128,6 +128,13 @@ int tdg_to_bf16(const float* p, void* o, long long n, hipStream_t st);
 int tdg_transpose_grouped(const void* const* src, void* const* dst, int G, int R, int C,
                           hipStream_t st);
 
+// ----------------------------------------------------------------- ema.hip
+// e[0, n) += (p - e) * (1 - d_eff), d_eff from decay, warmup and the device
+// update count (count == 0: e = p); gstate as in tdg_adam (skipped step: no
+// write, no advance); inc_count: the last range of a step advances the count
+int tdg_ema(const float* p, float* e, long long n, long long* count, float decay, int warmup,
+            int inc_count, const float* gstate, hipStream_t st);
+
 // ------------------------------------ fp8_gemm.hip, fp8_wgrad.hip, fp8_quant.hip
 // afmt / cfmt / fmt: 0 e4m3, 1 e5m2; amax: a 2048-word slot (or slot table)
 int tdg_gemm_fp8(const void* A, const void* B, void* C, const float* bias, const float* sa,

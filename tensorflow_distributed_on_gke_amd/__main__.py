@@ -1,8 +1,9 @@
 """Command line entry point.
 
     python -m tensorflow_distributed_on_gke_amd train [--config FILE] [--set key=value ...] [--nproc N]
-    python -m tensorflow_distributed_on_gke_amd test  --weights PREFIX [--sentence TEXT ...] [--beam N]
+    python -m tensorflow_distributed_on_gke_amd test  --weights PREFIX [--ema] [--sentence TEXT ...] [--beam N]
             [--sample N --temperature T --top-k K --top-p P --seed S] [--input FILE --output FILE [--batch N]]
+    python -m tensorflow_distributed_on_gke_amd average --inputs PREFIX PREFIX ... --output PREFIX
     python -m tensorflow_distributed_on_gke_amd heartbeat --port 3479
 
 `train` is the reference's `python -m distributed_training_transformer`
@@ -15,7 +16,11 @@ torch.distributed.run (RANK set) or with one process.
 `test` is the reference's test.py + Tester (greedy translation, or beam
 search with --beam N --length-penalty ALPHA, or --sample N translations drawn
 per sentence); with --input / --output it translates a file, one sentence per
-line, to source<TAB>hypothesis<TAB>score lines.
+line, to source<TAB>hypothesis<TAB>score lines; --ema decodes from the
+averaged weights a run with `ema_decay` wrote next to the snapshot
+(`<weights>_ema`).
+`average` is checkpoint averaging: the mean of several weight bundles (float64
+on the host) as one f32 bundle `test --weights` and `warm_start` load.
 """
 from __future__ import annotations
 
@@ -94,7 +99,13 @@ def cmd_test(args) -> int:
         tok = ByteTokenizer(min(settings.src_vocab, settings.tgt_vocab))
     model = build_model(settings, dev)
     if args.weights:
-        bundle.load_weights(model.store, args.weights)
+        prefix = bundle.resolve_prefix(args.weights)
+        if args.ema:
+            prefix += bundle.EMA_SUFFIX
+            if not os.path.exists(prefix + ".index"):
+                raise FileNotFoundError(f"test --ema: no averaged weights at {prefix} (written next to a "
+                                        "snapshot by a run with ema_decay > 0)")
+        bundle.load_weights(model.store, prefix)
     tester = Tester(tok, model)
     mode = dict(beam=args.beam, alpha=args.length_penalty, sample=args.sample,
                 temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
@@ -115,6 +126,14 @@ def cmd_test(args) -> int:
         for h in (t if args.sample > 0 else [t]):
             print(f"{s!r} -> {h!r}")
     print("attention maps:", {k: tuple(v.shape) for k, v in attn.items()})
+    return 0
+
+
+def cmd_average(args) -> int:
+    from tensorflow_distributed_on_gke_amd.checkpoint import bundle
+
+    n = bundle.average_bundles(args.inputs, args.output)
+    print(f"average of {len(args.inputs)} bundles ({n} tensors) -> {args.output}")
     return 0
 
 
@@ -143,6 +162,8 @@ def main(argv=None) -> int:
     t.add_argument("--master-port", type=int, default=int(os.environ.get("MASTER_PORT", 3480)))
     e = sub.add_parser("test", parents=[common])
     e.add_argument("--weights", default=None, help="weights prefix or directory")
+    e.add_argument("--ema", action="store_true",
+                   help="load the averaged weights saved next to --weights (<prefix>_ema)")
     e.add_argument("--sentence", action="append", default=None)
     e.add_argument("--max-length", type=int, default=20)
     e.add_argument("--beam", type=int, default=1, help="beam width (1 = greedy, at most 8)")
@@ -158,10 +179,16 @@ def main(argv=None) -> int:
     e.add_argument("--output", default=None, metavar="FILE",
                    help="source<TAB>hypothesis<TAB>score lines, in input order")
     e.add_argument("--batch", type=int, default=32, help="sentences per batch of --input")
+    a = sub.add_parser("average")
+    a.add_argument("--inputs", nargs="+", required=True, metavar="PREFIX",
+                   help="weight bundles (prefixes or snapshot directories) of one model")
+    a.add_argument("--output", required=True, metavar="PREFIX")
     h = sub.add_parser("heartbeat")
     h.add_argument("--port", type=int, default=3479)
     args = ap.parse_args(argv)
     if args.cmd == "test":
+        if args.ema and not args.weights:
+            ap.error("test: --ema needs --weights")
         if (args.input is None) != (args.output is None) or (args.input and args.sentence):
             ap.error("test: --input and --output go together, without --sentence")
         if args.beam > 1 and args.sample > 0:
@@ -170,7 +197,8 @@ def main(argv=None) -> int:
             ap.error("test: --batch must be at least 1 and --sample at least 0")
     if args.cmd == "test" and not args.sentence and not args.input:
         args.sentence = ["muitas pessoas vieram à estação."]  # reference test.py:9
-    return {"train": cmd_train, "test": cmd_test, "heartbeat": cmd_heartbeat}[args.cmd](args)
+    return {"train": cmd_train, "test": cmd_test, "average": cmd_average,
+            "heartbeat": cmd_heartbeat}[args.cmd](args)
 
 
 if __name__ == "__main__":

@@ -21,7 +21,9 @@ object-graph bytes live in the data blob it does not ship, so that entry is
 not byte-verified (documented divergence).
 
 Extension over the reference: `save_training_state` writes a second bundle with
-the Adam slots and the iteration counter so training can resume exactly.
+the Adam slots and the iteration counter so training can resume exactly; with
+a weight EMA (train/ema.py) also the averaged weights, under `ema/<weight
+key>`, and their update count, `training_state/ema_updates`.
 """
 from __future__ import annotations
 
@@ -39,6 +41,8 @@ DT_FLOAT = 1
 DT_INT64 = 9
 OBJECT_GRAPH_KEY = "_CHECKPOINTABLE_OBJECT_GRAPH"
 SUFFIX = "/.ATTRIBUTES/VARIABLE_VALUE"
+EMA_PREFIX = "ema/"  # the averaged weights in the `_optimizer` bundle
+EMA_SUFFIX = "_ema"  # `<weights prefix>_ema`: the averaged-weights sibling of a snapshot
 
 
 # ------------------------------------------------------------------ key order
@@ -120,9 +124,10 @@ def object_graph(keys: List[str]) -> bytes:
 
 
 # ------------------------------------------------------------------ tensors <-> TF layout
-def tf_tensors(store: ParamStore) -> Dict[str, np.ndarray]:
-    """{tf key: f32 numpy array in TF layout} from the f32 masters."""
-    host = store.flat.detach().float().cpu()
+def tf_tensors(store: ParamStore, flat: Optional[torch.Tensor] = None) -> Dict[str, np.ndarray]:
+    """{tf key: f32 numpy array in TF layout} from the f32 masters, or from
+    another flat buffer of the same layout (the averaged weights)."""
+    host = (store.flat if flat is None else flat).detach().float().cpu()
     out = {}
     for p in store.params:
         full = host[p.offset: p.offset + p.numel].view(p.shape)
@@ -189,17 +194,24 @@ def save_weights(store: ParamStore, prefix: str) -> None:
     write_bundle(prefix, tf_tensors(store))
 
 
-def load_weights(store: ParamStore, prefix: str, strict: bool = True) -> List[str]:
-    """Keras `model.load_weights(prefix)` equivalent. Returns missing keys."""
-    tensors = read_bundle(resolve_prefix(prefix))
-    host = store.flat.detach().float().cpu().clone()
+def save_ema_weights(store: ParamStore, ema, prefix: str) -> str:
+    """The averaged weights of a WeightEma as the `<prefix>_ema` sibling of a
+    weights bundle: same keys, order and layout (the directory's `checkpoint`
+    state file keeps naming the raw weights). Returns the prefix written."""
+    write_bundle(prefix + EMA_SUFFIX, tf_tensors(store, ema.avg), state_file=False)
+    return prefix + EMA_SUFFIX
+
+
+def _scatter_tf(store: ParamStore, host: torch.Tensor, tensors: Dict[str, np.ndarray],
+                key_prefix: str = "") -> List[str]:
+    """TF-layout tensors into a host copy of a flat buffer. Returns missing keys."""
     missing = []
     for p in store.params:
         full = host[p.offset: p.offset + p.numel].view(p.shape)
         for s in p.tf:
-            a = tensors.get(s.key)
+            a = tensors.get(key_prefix + s.key)
             if a is None:
-                missing.append(s.key)
+                missing.append(key_prefix + s.key)
                 continue
             t = torch.from_numpy(a)
             if s.transpose:
@@ -207,6 +219,14 @@ def load_weights(store: ParamStore, prefix: str, strict: bool = True) -> List[st
             if tuple(t.shape) != tuple(full[s.row0: s.row1].shape):
                 raise ValueError(f"{s.key}: checkpoint shape {tuple(a.shape)} does not match model")
             full[s.row0: s.row1].copy_(t)
+    return missing
+
+
+def load_weights(store: ParamStore, prefix: str, strict: bool = True) -> List[str]:
+    """Keras `model.load_weights(prefix)` equivalent. Returns missing keys."""
+    tensors = read_bundle(resolve_prefix(prefix))
+    host = store.flat.detach().float().cpu().clone()
+    missing = _scatter_tf(store, host, tensors)
     if strict and missing:
         raise KeyError(f"checkpoint {prefix} lacks {len(missing)} variables, e.g. {missing[:3]}")
     store.flat.copy_(host.to(store.flat.device))
@@ -214,9 +234,39 @@ def load_weights(store: ParamStore, prefix: str, strict: bool = True) -> List[st
     return missing
 
 
+def average_bundles(inputs: List[str], output: str) -> int:
+    """Checkpoint averaging: the elementwise mean of the weight bundles
+    `inputs` (prefixes or snapshot directories), accumulated in float64 on
+    the host and rounded once to f32, written as a bundle with the same keys
+    and order. Inputs whose key sets or shapes differ are refused. Returns
+    the number of tensors."""
+    if not inputs:
+        raise ValueError("average: no input bundles")
+    acc: Dict[str, np.ndarray] = {}
+    for i, path in enumerate(inputs):
+        tensors = read_bundle(resolve_prefix(path))
+        if i == 0:
+            bad = [k for k, a in tensors.items() if a.dtype != np.float32]
+            if bad:
+                raise ValueError(f"average: {path} holds non-f32 tensors, e.g. {bad[:3]}")
+            acc = {k: a.astype(np.float64) for k, a in tensors.items()}
+            continue
+        if set(tensors) != set(acc):
+            diff = sorted(set(tensors) ^ set(acc))
+            raise ValueError(f"average: {path} and {inputs[0]} hold different keys, e.g. {diff[:3]}")
+        for k, a in tensors.items():
+            if a.shape != acc[k].shape or a.dtype != np.float32:
+                raise ValueError(f"average: {k} is {a.dtype}{a.shape} in {path} but "
+                                 f"float32{acc[k].shape} in {inputs[0]}")
+            acc[k] += a
+    write_bundle(output, {k: (a / len(inputs)).astype(np.float32) for k, a in acc.items()})
+    return len(acc)
+
+
 def save_training_state(store: ParamStore, opt, prefix: str, extra: Optional[Dict[str, int]] = None) -> None:
-    """Adam slots (m, v per variable, TF layout, Keras slot-style names) and
-    the iteration counter -> `<prefix>_optimizer` bundle (resume extension)."""
+    """Adam slots (m, v per variable, TF layout, Keras slot-style names), the
+    iteration counter and, with a weight EMA, the averaged weights and their
+    update count -> `<prefix>_optimizer` bundle (resume extension)."""
     m = opt.m.detach().float().cpu()
     v = opt.v.detach().float().cpu()
     out: Dict[str, np.ndarray] = {}
@@ -230,6 +280,10 @@ def save_training_state(store: ParamStore, opt, prefix: str, extra: Optional[Dic
                 out[s.key.replace(SUFFIX, f"/.OPTIMIZER_SLOT/optimizer/{name}/.ATTRIBUTES/VARIABLE_VALUE")] = \
                     np.ascontiguousarray(t.numpy())
     out["optimizer/iter/.ATTRIBUTES/VARIABLE_VALUE"] = np.array(opt.iterations, dtype=np.int64)
+    ema = getattr(opt, "ema", None)
+    if ema is not None:
+        out.update({EMA_PREFIX + k: a for k, a in tf_tensors(store, ema.avg).items()})
+        out["training_state/ema_updates"] = np.array(ema.updates, dtype=np.int64)
     for k, val in (extra or {}).items():
         out[f"training_state/{k}"] = np.array(int(val), dtype=np.int64)
     write_bundle(prefix + "_optimizer", out, order=lambda k: k, with_object_graph=False,
@@ -250,5 +304,17 @@ def load_training_state(store: ParamStore, opt, prefix: str) -> Dict[str, int]:
     opt.m.copy_(m.to(opt.m.device))
     opt.v.copy_(v.to(opt.v.device))
     opt.step.fill_(int(tensors["optimizer/iter/.ATTRIBUTES/VARIABLE_VALUE"].item()))
+    ema = getattr(opt, "ema", None)
+    if ema is not None:
+        # (a state written without an EMA: count 0, so the first update copies
+        # the weights; EMA entries with the EMA off are ignored)
+        ema.count.zero_()
+        if "training_state/ema_updates" in tensors:
+            avg = ema.avg.detach().float().cpu().clone()
+            missing = _scatter_tf(store, avg, tensors, EMA_PREFIX)
+            if missing:
+                raise KeyError(f"training state {prefix} lacks {len(missing)} EMA variables, e.g. {missing[:3]}")
+            ema.avg.copy_(avg.to(ema.avg.device))
+            ema.count.fill_(int(tensors["training_state/ema_updates"].item()))
     return {k[len("training_state/"):]: int(a.item()) for k, a in tensors.items()
             if k.startswith("training_state/")}

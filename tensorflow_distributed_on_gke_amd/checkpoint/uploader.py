@@ -126,7 +126,9 @@ class ModelUploader:
         self.cloud_root_folder: Optional[str] = None
         self.last_upload_folder: Optional[str] = None
 
-    def take_snapshot(self, model) -> None:
+    def take_snapshot(self, model, ema=None) -> None:
+        """ema (train/ema.py WeightEma with at least one update, or None): a
+        weights snapshot also gets the averaged weights, `model_weights_ema`."""
         if self.cloud_root_folder is None:
             save_initial_model(model, self.local_directory + "/initial_model")
             self.cloud_root_folder = safe_upload_directory(self.storage, self.local_directory,
@@ -135,6 +137,8 @@ class ModelUploader:
         else:
             save_dir = new_directory_name(self.local_directory + "/weights_snapshots/model_weights")
             bundle.save_weights(model.store, save_dir + "/model_weights")
+            if ema is not None and ema.updates > 0:
+                bundle.save_ema_weights(model.store, ema, save_dir + "/model_weights")
             self.last_upload_folder = safe_upload_directory(
                 self.storage, save_dir, self.cloud_root_folder + "/weights_snapshot")
 

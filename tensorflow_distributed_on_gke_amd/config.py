@@ -51,6 +51,15 @@ class Settings:
     # (weights, moments and `iterations` untouched)
     global_clipnorm: float = 0.0
     skip_nonfinite: bool = False
+    # extension, off by default: an exponential moving average of the weights
+    # (Keras Adam use_ema; train/ema.py), updated after every completed step.
+    # ema_decay in [0, 1), 0: off; ema_warmup: the decay ramps up as
+    # min(ema_decay, (1 + updates) / (10 + updates)); ema_eval: a second
+    # validation pass per epoch on the averaged weights. With it on, weight
+    # snapshots gain a `model_weights_ema` bundle (`test --ema` decodes from it)
+    ema_decay: float = 0.0
+    ema_warmup: bool = False
+    ema_eval: bool = True
     # --- loop (reference __main__.py:89, 149-180)
     epochs: int = 20
     steps_per_epoch: int = 200
@@ -149,4 +158,6 @@ def load_settings(path: Optional[str] = None, overrides: Optional[List[str]] = N
         if k not in names:
             raise KeyError(f"unknown setting {k!r}")
         setattr(s, k, _coerce(getattr(s, k), v, names[k].type))
+    if not (isinstance(s.ema_decay, (int, float)) and 0.0 <= float(s.ema_decay) < 1.0):
+        raise ValueError(f"ema_decay must lie in [0, 1) (0: off), got {s.ema_decay!r}")
     return s

@@ -945,6 +945,16 @@ def grad_norm_finalize(partials, nparts, state, counters, clip=0.0, skip_nonfini
     C().grad_norm_finalize(partials, nparts, state, counters, clip, skip_nonfinite, grad_scale)
 
 
+def ema_update(p, e, count, decay, warmup=False, inc_count=True, norm_state=None):
+    """e += (p - e) * (1 - d_eff) over two f32 ranges of one size (ema.hip):
+    d_eff = decay, or with warmup min(decay, (1 + count) / (10 + count));
+    count (int64 [1], device) is the number of updates so far -- at 0 the
+    update copies p into e -- and advances when inc_count is set (the last
+    range of a step). norm_state: see adam(); a skipped step changes neither
+    e nor count."""
+    C().ema(p, e, count, decay, warmup, inc_count, norm_state)
+
+
 # ------------------------------------------------------------------ stream signal
 class StreamSignal:
     """A host-visible position marker on a HIP stream (csrc/kernels/signal.hip):

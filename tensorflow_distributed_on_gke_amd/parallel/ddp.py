@@ -207,6 +207,9 @@ class DataParallel:
         self._pos = {p.index: i for i, p in enumerate(self._order)}
         self._comm_bufs = {}
         self.opt = None
+        # the optimizer's weight EMA (train/ema.py), if any: verify_replicas()
+        # checks it too (TrainStep sets it)
+        self.ema = None
         self._upd_stream = None
         # a train/graphs.SegmentedGraph while the step is being captured: the
         # collectives become host calls between graph segments
@@ -535,17 +538,27 @@ class DataParallel:
                 self.opt.apply_range(b.start, b.end, inc_step=False)
         if self.opt is not None:
             self.opt.advance_step()
+            if getattr(self.opt, "ema", None) is not None:
+                self.opt.update_ema()  # once per completed step, after the last Adam range
         self.reset()
 
     def verify_replicas(self) -> None:
         """Debug check (race / divergence detection): every rank's weights must
         be bitwise identical after a synchronous step. Compares an exact
-        checksum (sum of the int32 bit patterns, int64) across ranks."""
+        checksum (sum of the int32 bit patterns, int64) across ranks; with a
+        weight EMA, also of the average and its update count."""
         if self.world <= 1:
             return
         self.check_quiescent("verify_replicas")
-        bits = self.store.flat.detach().view(torch.int32)
-        local = torch.stack([bits.sum(dtype=torch.int64), (bits.to(torch.int64) * 2654435761).sum()])
+
+        def sums(t: torch.Tensor) -> List[torch.Tensor]:
+            bits = t.detach().view(torch.int32)
+            return [bits.sum(dtype=torch.int64), (bits.to(torch.int64) * 2654435761).sum()]
+
+        local = sums(self.store.flat)
+        if self.ema is not None:
+            local += sums(self.ema.avg) + [self.ema.count.sum()]
+        local = torch.stack(local)
         allv = [torch.zeros_like(local) for _ in range(self.world)]
         dist.all_gather(allv, local, group=self.group)
         ref = allv[0]

@@ -17,7 +17,11 @@ Reference: distributed_training_transformer/__main__.py:34-186. Behaviour kept:
 Extensions: resume from the newest local training state (weights + Adam
 slots + epoch) written by the chief every epoch, broadcast to all ranks; HIP
 graph capture of the step; tokens/s in the epoch line; `kill_at_step`
-failure injection for the launcher's failure-detection tests.
+failure injection for the launcher's failure-detection tests; with `ema_decay`
+an exponential moving average of the weights (train/ema.py), resumed and
+broadcast with the optimizer state, validated in a second pass per epoch
+("EMA Test Loss ..." line, `ema_eval`) and written next to every weights
+snapshot as `model_weights_ema`.
 
 Metric reads are the only host syncs: the device accumulators are summed over
 ranks (one small all-reduce) at log points, not every step.
@@ -99,7 +103,8 @@ class Trainer:
         self.model = build_model(s, info.device)
         self.opt = Adam(self.model.store, self.model.cfg.d_model, warmup=s.warmup_steps, beta1=s.beta1,
                         beta2=s.beta2, eps=s.epsilon, lr=s.learning_rate,
-                        global_clipnorm=s.global_clipnorm, skip_nonfinite=s.skip_nonfinite)
+                        global_clipnorm=s.global_clipnorm, skip_nonfinite=s.skip_nonfinite,
+                        ema_decay=s.ema_decay, ema_warmup=s.ema_warmup)
         comm = torch.bfloat16 if s.grad_comm_dtype == "bf16" else None
         self.ddp = (DataParallel(self.model.store, bucket_mb=s.bucket_mb, comm_dtype=comm)
                     if info.world > 1 else None)
@@ -153,7 +158,10 @@ class Trainer:
     def _broadcast_state(self) -> None:
         if self.info.world > 1:
             self._quiet("broadcast")
-            for t in (self.model.store.flat, self.opt.m, self.opt.v, self.opt.step):
+            ts = [self.model.store.flat, self.opt.m, self.opt.v, self.opt.step]
+            if self.opt.ema is not None:
+                ts += [self.opt.ema.avg, self.opt.ema.count]
+            for t in ts:
                 dist.broadcast(t, 0)
             self.model.store.refresh_compute()
 
@@ -169,6 +177,9 @@ class Trainer:
                 flag[0], flag[1] = 1, extra.get("epoch", 0)
                 self.log(f"Resuming from {self.resume_prefix} at epoch {extra.get('epoch', 0) + 1}, "
                          f"iteration {self.opt.iterations}")
+                if self.opt.ema is not None and "ema_updates" not in extra:
+                    self.log("note: the training state holds no weight EMA; the average restarts "
+                             "from the weights at the next step")
             elif s.warm_start:
                 bundle.load_weights(self.model.store, s.warm_start)
                 self.log(f"Warm start from {s.warm_start}")
@@ -190,7 +201,7 @@ class Trainer:
             storage = make_storage(s.cloud_storage_bucket_name, s.google_cloud_access_key_path,
                                    s.storage_backend, s.storage_root)
             self.uploader = ModelUploader(storage, s.cloud_storage_upload_folder, s.temporary_directory)
-        self.uploader.take_snapshot(self.model)
+        self.uploader.take_snapshot(self.model, ema=self.opt.ema)
 
     # ------------------------------------------------------------------ metrics
     def _reduce(self, t: torch.Tensor) -> torch.Tensor:
@@ -230,6 +241,15 @@ class Trainer:
             K.check_trailing_padding()
         n = max(float(a[2]), 1.0)
         return {"loss": float(a[0]) / n, "acc": float(a[1]) / n}
+
+    def validate_ema(self) -> Optional[Dict[str, float]]:
+        """validate() on the averaged weights (exchanged with the weights in
+        place for the pass); None before the first EMA update."""
+        ema = self.opt.ema
+        if ema is None or ema.updates == 0:
+            return None
+        with ema.swapped():
+            return self.validate()
 
     def _arm_backward_fault(self) -> None:
         """kill_point=backward: this rank exits inside the backward of step
@@ -346,6 +366,9 @@ class Trainer:
                 self._snapshot()
                 self.log(f"Saving checkpoint for epoch {epoch + 1} at {self.uploader.last_upload_location()}")
             val = self.validate()
+            ema_val = self.validate_ema() if s.ema_eval else None
+            ema_rec = {} if ema_val is None else {"ema_test_loss": ema_val["loss"],
+                                                  "ema_test_acc": ema_val["acc"]}
             if info.chief and s.resume:
                 self.save_resume_state(epoch + 1)
             dt = time.time() - t0
@@ -353,10 +376,12 @@ class Trainer:
                             epoch_tokens / max(train_time, 1e-9))
             self.history.append(st)
             self.timer.drain()
-            self.metrics.write(kind="epoch", **st.__dict__, **self._clip_record())
+            self.metrics.write(kind="epoch", **st.__dict__, **ema_rec, **self._clip_record())
             if info.chief:
                 self.log(f"Epoch {epoch + 1} Loss {train_loss:.4f} Accuracy {train_acc:.4f} "
                          f"Test Loss {val['loss']:.4f} Test Accuracy {val['acc']:.4f}")
+                if ema_val is not None:
+                    self.log(f"EMA Test Loss {ema_val['loss']:.4f} Test Accuracy {ema_val['acc']:.4f}")
                 self.log(f"Time taken for 1 epoch: {dt:.2f} secs ({st.tokens_per_s:,.0f} tokens/s)\n")
             if info.world > 1:
                 self._quiet("epoch barrier")

@@ -13,6 +13,10 @@ the factor and the skip flag live in device memory (grad_sumsq /
 grad_norm_finalize in adam.hip) and the Adam kernels read them there, so the
 step still needs no host sync.
 
+`ema_decay` (off by default; Keras Adam's `use_ema` / `ema_momentum`) keeps an
+exponential moving average of the weights (train/ema.py WeightEma, `opt.ema`),
+updated once per completed step after the last Adam range.
+
 Reference: distributed_training_transformer/__main__.py:72-73
 (Adam(learning_rate=NoamSchedule(d_model), beta_1=0.9, beta_2=0.98, epsilon=1e-9)).
 """
@@ -25,6 +29,7 @@ import torch
 
 from tensorflow_distributed_on_gke_amd.models.params import ParamStore
 from tensorflow_distributed_on_gke_amd.ops import kernels as K
+from tensorflow_distributed_on_gke_amd.train.ema import WeightEma, check_decay
 from tensorflow_distributed_on_gke_amd.train.schedule import noam_lr
 
 
@@ -37,7 +42,8 @@ class Adam:
     def __init__(self, store: ParamStore, d_model: int, warmup: float = 4000.0, beta1: float = 0.9,
                  beta2: float = 0.98, eps: float = 1e-9, lr: Optional[float] = None,
                  weight_decay: float = 0.0, global_clipnorm: float = 0.0,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, ema_decay: float = 0.0, ema_warmup: bool = False):
+        ema_decay = check_decay(ema_decay)
         if not (0.0 <= float(global_clipnorm) < math.inf):
             raise ValueError(f"global_clipnorm must be finite and >= 0 (0: off), got {global_clipnorm!r}")
         self.store = store
@@ -75,6 +81,13 @@ class Adam:
                                              device=dev)
             else:
                 self._sumsq = torch.zeros((), dtype=torch.float64)
+        # the averaged weights (None with ema_decay 0: no launch is added)
+        self.ema: Optional[WeightEma] = WeightEma(store, ema_decay, ema_warmup) if ema_decay > 0.0 else None
+
+    def update_ema(self) -> None:
+        """The EMA update of a completed step (after its last Adam range)."""
+        if self.ema is not None:
+            self.ema.update(self.norm_state)
 
     @property
     def clip_on(self) -> bool:
@@ -184,6 +197,8 @@ class Adam:
         False -- nothing done -- when its chunk table is unavailable). With
         clipping or skipping on, the norm pass over the whole buffer first."""
         s = self.store
+        if self.ema is not None:
+            self.ema.check_not_swapped("optimizer step")
         if fp8w is not None:
             chunks = fp8w.adam_chunks(s) if s.flat.is_cuda and s.flat_compute is not None else None
             if chunks is None:
@@ -196,10 +211,12 @@ class Adam:
                           0 if self.lr_const is not None else 1, self.zero_grad, True,
                           fp8w.meta.scale, fp8w.meta.amax, norm_state=self.norm_state)
             s.refresh_transposed(0, s.total)
+            self.update_ema()
             return True
         if self.clip_on:
             self.compute_norm(grad_scale)
         self.apply_range(0, self.store.total, grad_scale, inc_step=True)
+        self.update_ema()
         return True
 
     def apply_range(self, start: int, end: int, grad_scale: float = 1.0, inc_step: bool = True) -> None:
@@ -210,6 +227,8 @@ class Adam:
         caller has run accumulate_norm() over every range of the step and
         finalize_norm() first (apply() and DataParallel.finish() do)."""
         s = self.store
+        if self.ema is not None:
+            self.ema.check_not_swapped("optimizer step")
         sl = slice(start, end)
         ns = self.norm_state
         tab = self._chunk_table(start, end)

@@ -66,6 +66,8 @@ class TrainStep:
         self.model = model
         self.opt = opt
         self.ddp = ddp
+        if ddp is not None:
+            ddp.ema = opt.ema  # (verify_replicas also compares the averaged weights)
         self.workers = float(workers)
         # global token mean: every replica's loss is normalised by the label
         # count of the whole global batch (one scalar all-reduce per step,
@@ -158,6 +160,8 @@ class TrainStep:
             ts += [self.fp8.meta.scale, self.fp8.gmeta.scale]
         if self.opt.clip_on:
             ts += [self.opt.norm_state, self.opt.norm_counters]
+        if self.opt.ema is not None:
+            ts += [self.opt.ema.avg, self.opt.ema.count]
         return ts
 
     def snapshot(self):
@@ -440,6 +444,8 @@ class TrainStep:
         return out
 
     def __call__(self, src: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
+        if self.opt.ema is not None:  # (a replayed graph runs no Python: checked here)
+            self.opt.ema.check_not_swapped("training step")
         if not self.captured:
             return self.eager(src, tgt)
         if src.shape != self._static[0].shape or tgt.shape != self._static[1].shape:
