@@ -14,6 +14,39 @@ void count_tokens(const Tensor& labels, const Tensor& out) {
             "tdg count_tokens");
 }
 
+// tgts: the target batches [B, T1] of one optimizer update; total f32 [1];
+// counts (optional) int32 [>= len(tgts)]
+void count_labels_multi(const std::vector<Tensor>& tgts, const Tensor& total,
+                        const optional<Tensor>& counts) {
+  const int n = (int)tgts.size();
+  TORCH_CHECK(n >= 1, "count_labels_multi: no entries");
+  check_f32(total, "total");
+  TORCH_CHECK(total.numel() >= 1, "count_labels_multi: total");
+  if (counts.has_value())
+    TORCH_CHECK(counts->is_cuda() && counts->scalar_type() == at::kInt && counts->is_contiguous() &&
+                    counts->numel() >= n, "count_labels_multi: counts must be int32 [n]");
+  std::vector<const void*> p(n);
+  std::vector<int> B(n), T1(n), t64(n);
+  for (int i = 0; i < n; ++i) {
+    const Tensor& t = tgts[i];
+    TORCH_CHECK(t.is_cuda() && t.dim() == 2 && t.is_contiguous() && t.device() == total.device(),
+                "count_labels_multi: entries must be contiguous [B, T1] tensors on one GPU");
+    const auto dt = t.scalar_type();
+    TORCH_CHECK(dt == at::kLong || dt == at::kInt, "count_labels_multi: tokens must be int64 or int32");
+    TORCH_CHECK(t.numel() <= 0x7fffffffLL, "count_labels_multi: entry too large");
+    p[i] = t.data_ptr();
+    B[i] = (int)t.size(0);
+    T1[i] = (int)t.size(1);
+    t64[i] = dt == at::kLong;
+  }
+  c10::DeviceGuard g(total.device());
+  check_err(tdg_count_labels_multi(p.data(), B.data(), T1.data(), t64.data(), n,
+                                   total.data_ptr<float>(),
+                                   counts.has_value() ? counts->data_ptr<int>() : nullptr,
+                                   stream_of(total)),
+            "tdg count_labels_multi");
+}
+
 // tgt_in, labels [B, T] (token dtype), src_len, tgt_len [B] int32, ntok [1] f32,
 // ctr (optional int64 [1], += 1)
 void prep_batch(const Tensor& src, const Tensor& tgt, const Tensor& tgt_in, const Tensor& labels,
@@ -95,6 +128,7 @@ void xent_stats(const Tensor& row_loss, const Tensor& row_correct, const Tensor&
 
 void def_loss(py::module_& m) {
   m.def("count_tokens", &count_tokens);
+  m.def("count_labels_multi", &count_labels_multi);
   m.def("prep_batch", &prep_batch);
   m.def("xent", &xent);
   m.def("xent_stats", &xent_stats);

@@ -99,6 +99,11 @@ int tdg_count_tokens(const void* labels, int lab64, int M, float* out, hipStream
 int tdg_prep_batch(const void* src, int S, const void* tgt, int T1, int B, int lab64, void* tgt_in,
                    void* labels, int* src_len, int* tgt_len, float* ntok, long long* ctr,
                    int* row_lab, unsigned* ticket, int* bad_rows, hipStream_t st);
+// up to 32 target batches [B[i], T1[i]] (host arrays of device pointers and
+// sizes): total[0] = labels (tgt[b, t] != 0, t >= 1) of all of them, as f32;
+// counts (or null): int32 per entry. -1: n outside [1, 32]; -2: a bad entry
+int tdg_count_labels_multi(const void* const* tgt, const int* B, const int* T1, const int* tok64,
+                           int n, float* total, int* counts, hipStream_t st);
 int tdg_xent(void* logits, int M, int V, int ldl, const void* labels, int lab64, const float* ntok,
              float workers, float smoothing, float* row_loss, float* row_correct, int write_grad,
              hipStream_t st);

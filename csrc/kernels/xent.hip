@@ -343,6 +343,52 @@ __global__ __launch_bounds__(1024) void xent_stats_kernel(const float* __restric
   }
 }
 
+// The label count of a whole optimizer update in one launch (gradient
+// accumulation with loss_mode=global_mean: every micro-batch's cross entropy
+// divides by the labels of all of them, so the total must exist before the
+// first one runs). Up to COUNT_MAX_ENTRIES target batches [B, T1], passed by
+// value; labels are tgt[b, t] for t >= 1, counted when != PAD (0). One
+// workgroup of 16 waves, each taking entries round-robin; integer counts
+// (exact, order-independent), the total stored once as f32 -- the `ntok`
+// scalar the update's tdg_xent / tdg_xent_stats launches read. No atomics, no
+// zeroed scratch.
+constexpr int COUNT_MAX_ENTRIES = 32;
+struct CountEntries {
+  const void* tgt[COUNT_MAX_ENTRIES];
+  int numel[COUNT_MAX_ENTRIES];  // B * T1
+  int t1[COUNT_MAX_ENTRIES];
+  unsigned tok64;                // bit i: entry i holds int64 tokens
+  int n;
+};
+
+__global__ __launch_bounds__(1024) void count_labels_multi_kernel(CountEntries e,
+                                                                  float* __restrict__ total,
+                                                                  int* __restrict__ counts) {
+  __shared__ int cnt[COUNT_MAX_ENTRIES];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int i = w; i < e.n; i += 16) {
+    const int n = e.numel[i], T1 = e.t1[i];
+    int c = 0;
+    if ((e.tok64 >> i) & 1u) {
+      const long long* t = static_cast<const long long*>(e.tgt[i]);
+      for (int j = lane; j < n; j += 64) c += (j % T1 != 0) && t[j] != 0;
+    } else {
+      const int* t = static_cast<const int*>(e.tgt[i]);
+      for (int j = lane; j < n; j += 64) c += (j % T1 != 0) && t[j] != 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if (lane == 0) cnt[i] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x < e.n && counts) counts[threadIdx.x] = cnt[threadIdx.x];
+  if (threadIdx.x == 0) {
+    long long s = 0;
+    for (int i = 0; i < e.n; ++i) s += cnt[i];
+    total[0] = (float)s;
+  }
+}
+
 }  // namespace tdg
 
 using namespace tdg;
@@ -354,6 +400,27 @@ extern "C" int tdg_count_tokens(const void* labels, int lab64, int M, float* out
   else
     hipLaunchKernelGGL(count_tokens_kernel<int>, dim3(1), dim3(256), 0, st, (const int*)labels, M,
                        out);
+  return 0;
+}
+
+// tgt[i]: device [B[i], T1[i]] contiguous tokens (int64 when tok64[i]); the
+// arrays themselves are host memory. total: f32 [1]; counts: int32 [n] or
+// null. -1: n outside [1, 32]; -2: an entry with B < 1, T1 < 2 or B * T1
+// beyond int32; nothing launched.
+extern "C" int tdg_count_labels_multi(const void* const* tgt, const int* B, const int* T1,
+                                      const int* tok64, int n, float* total, int* counts,
+                                      hipStream_t st) {
+  if (n < 1 || n > COUNT_MAX_ENTRIES) return -1;
+  CountEntries e = {};
+  e.n = n;
+  for (int i = 0; i < n; ++i) {
+    if (B[i] < 1 || T1[i] < 2 || (long long)B[i] * T1[i] > 0x7fffffffLL || !tgt[i]) return -2;
+    e.tgt[i] = tgt[i];
+    e.numel[i] = B[i] * T1[i];
+    e.t1[i] = T1[i];
+    if (tok64[i]) e.tok64 |= 1u << i;
+  }
+  hipLaunchKernelGGL(count_labels_multi_kernel, dim3(1), dim3(1024), 0, st, e, total, counts);
   return 0;
 }
 

@@ -116,6 +116,12 @@ class Settings:
     # losses / all replicas' label count (equal to the single-process loss on
     # the global batch, whatever the per-replica token counts)
     loss_mode: str = "replica_mean"
+    # extension, off at 1: gradient accumulation. One optimizer update consumes
+    # accum_steps consecutive local batches per rank (micro-batches), each
+    # treated as one more replica: the update is that of world * accum_steps
+    # replicas with one batch each (train/step.py TrainStep.update). An integer
+    # in [1, 32]; not with dtype=fp8
+    accum_steps: int = 1
 
     def global_batch(self, world: int) -> int:
         return self.local_batch_size * world
@@ -160,4 +166,19 @@ def load_settings(path: Optional[str] = None, overrides: Optional[List[str]] = N
         setattr(s, k, _coerce(getattr(s, k), v, names[k].type))
     if not (isinstance(s.ema_decay, (int, float)) and 0.0 <= float(s.ema_decay) < 1.0):
         raise ValueError(f"ema_decay must lie in [0, 1) (0: off), got {s.ema_decay!r}")
+    check_accum_steps(s.accum_steps, s.dtype)
     return s
+
+
+ACCUM_STEPS_MAX = 32
+
+
+def check_accum_steps(n: Any, dtype: str = "bf16") -> int:
+    """accum_steps is an integer in [1, 32], and 1 with dtype=fp8 (delayed
+    scaling across micro-batches is not designed yet); ValueError otherwise."""
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= ACCUM_STEPS_MAX:
+        raise ValueError(f"accum_steps must be an integer in [1, {ACCUM_STEPS_MAX}], got {n!r}")
+    if n > 1 and dtype == "fp8":
+        raise ValueError(f"accum_steps={n} with dtype=fp8 is not supported: the fp8 delayed scaling "
+                         "assumes one forward/backward per optimizer update (use dtype=bf16)")
+    return n

@@ -298,7 +298,8 @@ class Transformer:
     def loss_and_backward(self, src, tgt, rt: RunCtx, workers: float,
                           accum: Optional[torch.Tensor] = None, backward: bool = True,
                           step_out: Optional[torch.Tensor] = None,
-                          bump_ctr: bool = False, ntok_sum=None) -> torch.Tensor:
+                          bump_ctr: bool = False, ntok_sum=None,
+                          ntok_total: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Teacher-forced forward, masked CE / accuracy, and (if `backward`)
         the full backward into the flat gradient buffer. Returns a device
         tensor [local_loss, accuracy] (loss already / workers, as the
@@ -306,7 +307,14 @@ class Transformer:
         bump_ctr: advance the dropout RNG step counter rt.ctr first.
         ntok_sum: global-token-mean loss -- called with this replica's label
         count, turns it in place into the count over all replicas (returns an
-        async work handle or None); pass workers = 1 with it."""
+        async work handle or None); pass workers = 1 with it.
+        ntok_total: f32 [1] on the batch's device, the label count the loss is
+        normalised by instead of this batch's own (gradient accumulation under
+        the global token mean: the count of the whole update, known before
+        its first micro-batch -- ops.kernels.count_labels_multi); it is only
+        read. Pass workers = 1 with it and no ntok_sum."""
+        if ntok_total is not None and ntok_sum is not None:
+            raise ValueError("loss_and_backward: ntok_total and ntok_sum exclude each other")
         cfg = self.cfg
         dev = src.device
         if dev.type == "cuda":  # split / lengths / token count / ctr: one launch
@@ -315,6 +323,8 @@ class Transformer:
             lengths = (src_len, tgt_len)
             # the label count all-reduce flies during the forward
             ntok_work = ntok_sum(ntok) if ntok_sum is not None else None
+            if ntok_total is not None:
+                ntok = ntok_total
         else:
             if bump_ctr:
                 rt.ctr.add_(1)
@@ -348,7 +358,7 @@ class Transformer:
             lg = self.project(dec.detach())
             lab = labels.reshape(-1)
             mask = (lab != PAD_ID).to(torch.float32)
-            ntok = mask.sum()
+            ntok = mask.sum() if ntok_total is None else ntok_total.reshape(()).clone()
             if ntok_sum is not None:
                 w = ntok_sum(ntok)
                 if w is not None:

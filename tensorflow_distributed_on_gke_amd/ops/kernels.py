@@ -848,6 +848,36 @@ def count_tokens(labels, out):
     C().count_tokens(labels, out)
 
 
+COUNT_MAX_ENTRIES = 32
+_LABEL_TOTAL: Dict[torch.device, Tuple[torch.Tensor, torch.Tensor]] = {}
+
+
+def label_total(device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The static (f32 [1] total, int32 [32] per-entry) outputs of
+    count_labels_multi on `device`: captured steps bake the total's address in
+    as their cross entropy's `ntok`."""
+    dev = torch.device(device)
+    if dev.index is None:  # "cuda" and "cuda:<current>" are one device
+        dev = torch.device(dev.type, torch.cuda.current_device())
+    t = _LABEL_TOTAL.get(dev)
+    if t is None:
+        t = _LABEL_TOTAL[dev] = (torch.empty(1, dtype=torch.float32, device=dev),
+                                 torch.empty(COUNT_MAX_ENTRIES, dtype=torch.int32, device=dev))
+    return t
+
+
+def count_labels_multi(tgts, total=None, counts=None) -> torch.Tensor:
+    """One launch: the non-PAD label count (tgt[:, 1:] != 0) of up to 32
+    target batches [B, T1] (int32 / int64, mixed), as f32 [1] in `total`
+    (default: the device's static scalar, label_total) and per entry in
+    `counts`. More than 32 entries raise and launch nothing."""
+    tgts = [t.contiguous() for t in tgts]
+    if total is None:
+        total, counts = label_total(tgts[0].device)
+    C().count_labels_multi(tgts, total, counts)
+    return total
+
+
 _PREP_SCRATCH: Dict[tuple, torch.Tensor] = {}
 
 

@@ -235,6 +235,12 @@ class DataParallel:
         # time: every later collective raises instead of risking a mismatched
         # sequence across ranks
         self.poisoned: Optional[str] = None
+        # gradient accumulation (TrainStep.update): set during every
+        # micro-batch of an update but the last. The gradients written then
+        # are partial sums, so the grad-ready, sync and release hooks launch
+        # nothing and track nothing; the last micro-batch's backward issues
+        # the spans as a plain step does
+        self.hold = False
         self.buckets: List[Bucket] = []       # this step's launched spans
         self.last_buckets: List[Bucket] = []  # the previous step's (introspection)
         if self.active:
@@ -448,6 +454,8 @@ class DataParallel:
             self._wait_now(h)
 
     def _on_ready(self, p: Param) -> None:
+        if self.hold:
+            return
         self._ready[self._pos[p.index]] = True
         while self._front < len(self._order) and self._ready[self._front]:
             self._front += 1
@@ -455,6 +463,8 @@ class DataParallel:
             self._launch_span(self._front_off())
 
     def _on_sync(self) -> None:
+        if self.hold:
+            return
         if self.overlap and self._front_off() - self._reduced >= self.min_elems:
             self._launch_span(self._front_off())
 
@@ -475,7 +485,7 @@ class DataParallel:
                 view.copy_(buf)
 
     def _on_release(self) -> None:
-        if self.opt is None:
+        if self.opt is None or self.hold:
             return
         ready = [b for b in self.buckets if b.work is not None and not b.updated]
         if not ready:
@@ -500,6 +510,8 @@ class DataParallel:
         every collective (device-side wait; no host sync). With an attached
         optimizer, also update every span not yet updated and advance the
         optimizer step."""
+        if self.hold:
+            raise RuntimeError("DataParallel.finish() inside a held (non-final) micro-batch")
         if not self.active:
             self.reset()
             return

@@ -21,7 +21,10 @@ failure injection for the launcher's failure-detection tests; with `ema_decay`
 an exponential moving average of the weights (train/ema.py), resumed and
 broadcast with the optimizer state, validated in a second pass per epoch
 ("EMA Test Loss ..." line, `ema_eval`) and written next to every weights
-snapshot as `model_weights_ema`.
+snapshot as `model_weights_ema`; with `accum_steps` = N > 1 gradient
+accumulation: an optimizer update takes N consecutive batches of the epoch
+(TrainStep.update), and steps, log points, fault injection and timings count
+updates.
 
 Metric reads are the only host syncs: the device accumulators are summed over
 ranks (one small all-reduce) at log points, not every step.
@@ -39,7 +42,7 @@ import torch.distributed as dist
 
 from tensorflow_distributed_on_gke_amd.checkpoint import bundle
 from tensorflow_distributed_on_gke_amd.checkpoint.uploader import ModelUploader, make_storage
-from tensorflow_distributed_on_gke_amd.config import Settings
+from tensorflow_distributed_on_gke_amd.config import Settings, check_accum_steps
 from tensorflow_distributed_on_gke_amd.data.synthetic import SyntheticPairs
 from tensorflow_distributed_on_gke_amd.models.layers import RunCtx
 from tensorflow_distributed_on_gke_amd.models.transformer import Transformer, model_config
@@ -83,6 +86,7 @@ class Trainer:
 
     def __post_init__(self):
         s, info = self.settings, self.info
+        check_accum_steps(s.accum_steps, s.dtype)
         if s.worker_count != info.world and info.chief:
             # the reference used worker_count both as expected size and loss
             # divisor; the runtime world size wins
@@ -113,10 +117,12 @@ class Trainer:
             from tensorflow_distributed_on_gke_amd.ops.fp8 import Fp8State
             self.fp8 = Fp8State(self.model)
         self.step_fn = TrainStep(self.model, self.opt, self.ddp, workers=info.world, seed=s.seed + 17,
-                                 fp8_state=self.fp8, loss_mode=s.loss_mode)
+                                 fp8_state=self.fp8, loss_mode=s.loss_mode, accum_steps=s.accum_steps)
+        # every micro-batch of every rank is one replica of the update
+        self._replicas = info.world * s.accum_steps
         # summed accuracy over replicas: a mean of per-replica ratios, or (global
         # token mean) already the global ratio
-        self._acc_div = 1 if self.step_fn.global_mean else info.world
+        self._acc_div = 1 if self.step_fn.global_mean else self._replicas
         if self.tokenizers is not None:
             from tensorflow_distributed_on_gke_amd.data.text import TextPairs
             st, tt = self.tokenizers
@@ -272,7 +278,9 @@ class Trainer:
         half = len(self.model.store.params) // 2
 
         def hook(_p):
-            if self.global_step + 1 != s.kill_at_step:
+            # (accumulation: the update's last micro-batch, when the peers sit
+            # in its collectives)
+            if self.global_step + 1 != s.kill_at_step or not self.step_fn.last_micro:
                 return
             seen[0] += 1
             if seen[0] == half:
@@ -290,9 +298,17 @@ class Trainer:
         if info.chief and s.snapshot_every_epochs > 0:
             self._snapshot()
             self.log("Initial model snapshot uploaded to " + self.uploader.last_upload_location())
-        steps = s.steps_per_epoch
+        # an epoch is steps_per_epoch batches whatever accum_steps is: update u
+        # takes the epoch's batches u * N .. u * N + N - 1, and the tail that
+        # does not fill an update is skipped (as data/text.py skips the tail
+        # that does not fill a global batch)
+        N = s.accum_steps
+        steps = s.steps_per_epoch // N
+        if steps < 1:
+            raise ValueError(f"steps_per_epoch={s.steps_per_epoch} batches do not fill one update of "
+                             f"accum_steps={N}")
         self.global_step = self.start_epoch * steps
-        self.train_data.seek(self.global_step)
+        self.train_data.seek(self.start_epoch * s.steps_per_epoch)
         captured = False
         # optional Chrome trace of the first profile_steps + 2 steps (rank 0)
         prof_cm = torch_profile(s.profile_dir if info.chief else None, active=s.profile_steps)
@@ -303,9 +319,12 @@ class Trainer:
             t0 = time.time()
             self.step_fn.accum.zero_()
             epoch_tokens = 0
+            if N > 1:  # the epoch's own first batch (the previous one's tail is skipped)
+                self.train_data.seek(epoch * s.steps_per_epoch)
             for batch in range(steps):
-                src, tgt = self._to_dev(self.train_data.next())
-                epoch_tokens += (src.shape[1] + tgt.shape[1] - 1) * src.shape[0] * info.world
+                micro = [self._to_dev(self.train_data.next()) for _ in range(N)]
+                src, tgt = micro[0]
+                epoch_tokens += sum((a.shape[1] + b.shape[1] - 1) * a.shape[0] for a, b in micro) * info.world
                 if s.hip_graph and info.device.type == "cuda" and not captured \
                         and not self._backward_fault_armed:
                     # capture() restores the state its warm-up steps changed,
@@ -322,7 +341,7 @@ class Trainer:
                         self.log("note: the step runs eagerly")
                     captured = True
                 self.timer.start()
-                self.step_fn(src, tgt)
+                self.step_fn.update(micro)
                 self.timer.stop()
                 self.global_step += 1
                 if prof_left:
@@ -342,7 +361,7 @@ class Trainer:
                     if info.device.type == "cuda":
                         K.check_trailing_padding()  # rows with interior PADs (device counter)
                     a = self._reduce(self.step_fn.accum)
-                    n = max(float(a[2]) / info.world, 1.0)
+                    n = max(float(a[2]) / self._replicas, 1.0)
                     st = summarize(self.timer.drain())
                     if info.chief:
                         self.log(f"Epoch {epoch + 1} Batch {batch} Loss {float(a[0]) / n:.4f} "
@@ -356,7 +375,7 @@ class Trainer:
                                            loss=float(a[0]) / n, accuracy=float(a[1]) / (n * self._acc_div),
                                            **st, **self._clip_record())
             a = self._reduce(self.step_fn.accum)
-            n = max(float(a[2]) / info.world, 1.0)
+            n = max(float(a[2]) / self._replicas, 1.0)
             train_loss = float(a[0]) / n
             train_acc = float(a[1]) / (n * self._acc_div)
             if info.device.type == "cuda":

@@ -6,6 +6,13 @@ backward (gradients into the flat buffer, bucketed RCCL all-reduce started
 from inside backward) -> wait for the buckets -> [gradient-norm pass, with
 Adam's global_clipnorm / skip_nonfinite] -> multi-tensor Adam.
 
+Gradient accumulation (accum_steps = N > 1, TrainStep.update): an update takes
+N micro-batches, each treated as one more replica -- loss divided by
+world * N (or, global token mean, by the label count of all of them) -- the
+first overwriting the flat gradient buffer, the rest adding to it (the
+kernels' beta = 1 paths); everything after backward (all-reduce spans, norm
+pass, Adam, EMA) runs once, in the last micro-batch.
+
 Reference: distributed_training_transformer/__main__.py:105-132 (train_step
 inside strategy.run, apply_gradients all-reduce, strategy.reduce(SUM) of the
 per-replica losses). The per-step loss stays on device; it is summed over
@@ -16,11 +23,12 @@ from __future__ import annotations
 import os
 import time
 from collections import OrderedDict
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
 
+from tensorflow_distributed_on_gke_amd.config import check_accum_steps
 from tensorflow_distributed_on_gke_amd.models.layers import RunCtx, WgradQueue
 from tensorflow_distributed_on_gke_amd.models.transformer import Transformer
 from tensorflow_distributed_on_gke_amd.parallel import ddp as _ddp_mod
@@ -35,7 +43,8 @@ CHUNKED_WGRAD = True
 # tiles per wave of the chunked schedule (0: one whole-K 256x256 tile per CU);
 # tests set small values to force problems to be cut across launches
 WAVE_TILES = 0
-# skip the optimizer's gradient zeroing (all GPU gradient writers overwrite)
+# skip the optimizer's gradient zeroing (all GPU gradient writers overwrite;
+# with gradient accumulation the first micro-batch of every update does)
 ZERO_GRAD_FREE = True
 # how a data-parallel step is captured (TrainStep.capture):
 #   "seg"  -- chain of HIP graphs cut at the collectives, which stay eager
@@ -59,27 +68,51 @@ DP_OVERLAP_OPT = "tail"
 FUSED_FP8_ADAM = True
 
 
+def micro_positions(n: int) -> List[str]:
+    """Where each of an update's n micro-batches stands: "only", or "first",
+    "middle"..., "last". The position decides what a micro-batch launches (the
+    first overwrites the gradients, the last reduces and optimizes), so it is
+    part of a captured micro-batch's cache key."""
+    return ["only"] if n == 1 else ["first"] + ["middle"] * (n - 2) + ["last"]
+
+
 class TrainStep:
     def __init__(self, model: Transformer, opt: Adam, ddp: Optional[DataParallel], workers: float,
                  seed: int = 0, dropout: Optional[float] = None, fp8_state=None,
-                 defer_wgrad: Optional[bool] = None, loss_mode: str = "replica_mean"):
+                 defer_wgrad: Optional[bool] = None, loss_mode: str = "replica_mean",
+                 accum_steps: int = 1):
+        self.accum_steps = check_accum_steps(accum_steps, "fp8" if fp8_state is not None else "bf16")
         self.model = model
         self.opt = opt
         self.ddp = ddp
         if ddp is not None:
             ddp.ema = opt.ema  # (verify_replicas also compares the averaged weights)
-        self.workers = float(workers)
+        # every micro-batch counts as one more replica
+        self.workers = float(workers) * self.accum_steps
         # global token mean: every replica's loss is normalised by the label
         # count of the whole global batch (one scalar all-reduce per step,
         # overlapped with the forward) and the gradients are SUM-reduced
         if loss_mode not in ("replica_mean", "global_mean"):
             raise ValueError(f"loss_mode must be replica_mean or global_mean, got {loss_mode!r}")
-        self.global_mean = loss_mode == "global_mean" and ddp is not None and ddp.world > 1
+        multi = ddp is not None and ddp.world > 1
+        self.global_mean = loss_mode == "global_mean" and (multi or self.accum_steps > 1)
         self._ntok_sum = None
+        # accumulation under the global token mean: the label count of the
+        # whole update (all ranks, all micro-batches), set by _begin_update()
+        # before the first micro-batch and read by every cross entropy
+        self._ntok_total: Optional[torch.Tensor] = None
+        dev = model.device
         if self.global_mean:
             self.workers = 1.0
-            self._ntok_sum = ddp.all_reduce_async
-        dev = model.device
+            if self.accum_steps == 1:
+                self._ntok_sum = ddp.all_reduce_async
+            elif dev.type == "cuda":
+                self._ntok_total = K.label_total(dev)[0]
+            else:
+                self._ntok_total = torch.zeros(1, dtype=torch.float32)
+        self._ntok_reduce = ddp.all_reduce_async if multi else None
+        # the micro-batch now running is its update's last (or only) one
+        self.last_micro = True
         self.rt = RunCtx(training=True, dropout=model.cfg.dropout if dropout is None else dropout,
                          seed=seed, ctr=torch.zeros(1, dtype=torch.int64, device=dev),
                          store=model.store, fp8=fp8_state)
@@ -100,7 +133,9 @@ class TrainStep:
             self.rt.wgrad.small_per_shape = fp8_state is not None and not self.rt.wgrad._chunking()
         self.fp8 = fp8_state
         if dev.type == "cuda" and not self.rt.accumulate and ZERO_GRAD_FREE:
-            opt.zero_grad = False  # every GPU gradient writer overwrites
+            # every GPU gradient writer overwrites (the first micro-batch of an
+            # update; the others run with rt.accumulate set)
+            opt.zero_grad = False
         mode = DP_OVERLAP_OPT
         # (fp8: the scale update and the e4m3 weight re-quantisation run after
         # ddp.finish(), when every bucket's Adam is done, so the per-bucket
@@ -129,6 +164,7 @@ class TrainStep:
         self.graph_cache = 64
         self._graphs: "OrderedDict[tuple, tuple]" = OrderedDict()
         self._key: Optional[tuple] = None
+        self._pos = "only"  # the current captured micro-batch's position
         self._pool = None
         self._cap_stream: Optional[torch.cuda.Stream] = None
         self._warm_stream: Optional[torch.cuda.Stream] = None
@@ -136,7 +172,7 @@ class TrainStep:
 
     @property
     def captured(self) -> bool:
-        return self.graph is not None or self.segments is not None
+        return self.graph is not None or self.segments is not None or bool(self._graphs)
 
     def capture_mode(self) -> str:
         """"single" (one graph, no collectives), "seg" or "0" (the
@@ -162,6 +198,11 @@ class TrainStep:
             ts += [self.opt.norm_state, self.opt.norm_counters]
         if self.opt.ema is not None:
             ts += [self.opt.ema.avg, self.opt.ema.count]
+        if self.accum_steps > 1:
+            # a capture between two micro-batches warms up on the partial sums
+            ts += [self.model.store.flat_grad]
+            if self._ntok_total is not None:
+                ts += [self._ntok_total]
         return ts
 
     def snapshot(self):
@@ -182,12 +223,68 @@ class TrainStep:
             self.fp8.meta.amax.copy_(st[-2])
             self.fp8.gmeta.amax.copy_(st[-1])
 
-    def eager(self, src: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
-        self.model.loss_and_backward(src, tgt, self.rt, self.workers, accum=self.accum,
-                                     step_out=self.last, bump_ctr=True, ntok_sum=self._ntok_sum)
+    def eager(self, src: torch.Tensor, tgt: torch.Tensor, pos: str = "only") -> torch.Tensor:
+        """One micro-batch, uncaptured: forward and backward, the gradients
+        overwriting the flat buffer ("only" / "first") or adding to it; the
+        update's last one ("only" / "last") also reduces and optimizes.
+        With accum_steps > 1 under the global token mean, _begin_update() must
+        have set the update's label count."""
+        first, last = pos in ("only", "first"), pos in ("only", "last")
+        self.rt.accumulate = not first
+        self.last_micro = last
         if self.ddp is not None:
-            self.ddp.finish()
-        self.optimize()
+            self.ddp.hold = not last
+        try:
+            self.model.loss_and_backward(src, tgt, self.rt, self.workers, accum=self.accum,
+                                         step_out=self.last, bump_ctr=True, ntok_sum=self._ntok_sum,
+                                         ntok_total=self._ntok_total)
+        finally:
+            self.rt.accumulate = False
+            self.last_micro = True
+            if self.ddp is not None:
+                self.ddp.hold = False
+        if last:
+            if self.ddp is not None:
+                self.ddp.finish()
+            self.optimize()
+        return self.last
+
+    def _begin_update(self, micro_batches) -> None:
+        """Accumulation under the global token mean: the label count of all
+        the update's micro-batches (GPU: one launch, ops.kernels
+        count_labels_multi) summed over the ranks -- one scalar all-reduce per
+        update -- into the scalar every cross entropy of the update reads."""
+        tot = self._ntok_total
+        if tot is None:
+            return
+        tgts = [t for _, t in micro_batches]
+        if tot.is_cuda:
+            K.count_labels_multi(tgts, tot, K.label_total(tot.device)[1])
+        else:
+            tot.fill_(float(sum(int((t[:, 1:] != 0).sum()) for t in tgts)))
+        if self._ntok_reduce is not None:
+            self._ntok_reduce(tot).wait()
+
+    def update(self, micro_batches: Sequence[Tuple[torch.Tensor, torch.Tensor]]) -> torch.Tensor:
+        """One optimizer update from accum_steps micro-batches (src, tgt),
+        which may differ in shape. Defined as the update of world *
+        accum_steps replicas with one batch each. Returns the device tensor
+        [loss share, accuracy] of the LAST micro-batch; the update's loss is
+        the sum of the shares, which `accum` collects ([sum of loss shares,
+        sum of accuracies, micro-batches, labels])."""
+        if len(micro_batches) != self.accum_steps:
+            raise ValueError(f"update() takes accum_steps={self.accum_steps} micro-batches, "
+                             f"got {len(micro_batches)}")
+        if self.accum_steps == 1:
+            return self(*micro_batches[0])
+        if self.opt.ema is not None:  # (a replayed graph runs no Python: checked here)
+            self.opt.ema.check_not_swapped("training step")
+        self._begin_update(micro_batches)
+        for (src, tgt), pos in zip(micro_batches, micro_positions(self.accum_steps)):
+            if self.captured:
+                self._replay(src, tgt, pos)
+            else:
+                self.eager(src, tgt, pos)
         return self.last
 
     def optimize(self) -> None:
@@ -213,7 +310,9 @@ class TrainStep:
     def capture(self, src: torch.Tensor, tgt: torch.Tensor, warmup: int = 2) -> bool:
         """Capture the whole step (fwd+bwd+optimizer) on static input buffers:
         one HIP graph on a single GPU; under data parallelism a segmented
-        graph whose collectives are eager calls between the segments.
+        graph whose collectives are eager calls between the segments. With
+        accum_steps > 1 that is one captured micro-batch per position an
+        update of this shape needs (first, middle, last: micro_positions).
 
         Warm-up steps run first (lazily-allocated workspaces, GEMM tunings,
         communication buffers); the training state is snapshotted before and
@@ -221,19 +320,26 @@ class TrainStep:
         model, optimizer and counters are exactly as they were. Returns False
         (and leaves the step eager) when the data-parallel step is configured
         not to be captured."""
-        mode = self.capture_mode()
-        if mode == "0":
+        if self.capture_mode() == "0":
             return False
+        if self._ntok_total is not None:
+            saved = self._ntok_total.clone()
+            self._begin_update([(src, tgt)] * self.accum_steps)  # what the warm-ups divide by
+        for pos in dict.fromkeys(micro_positions(self.accum_steps)):
+            self._capture_micro(src, tgt, pos, warmup)
+        if self._ntok_total is not None:
+            self._ntok_total.copy_(saved)
+        return True
+
+    def _capture_micro(self, src: torch.Tensor, tgt: torch.Tensor, pos: str, warmup: int) -> None:
+        """Capture one micro-batch at position `pos` (capture_mode() is not
+        "0") and make it the current cache entry."""
+        mode = self.capture_mode()
         if self._pool is None:
             self._pool = torch.cuda.graph_pool_handle()
-        if (self._static is not None and self._static[0].shape == src.shape
-                and self._static[1].shape == tgt.shape):
-            # (choose_dp_mode captures more than one arm: every captured graph
-            # reads the same static input buffers)
-            self._static[0].copy_(src)
-            self._static[1].copy_(tgt)
-        else:
-            self._static = (src.clone(), tgt.clone())
+        # (no current entry until this one is registered)
+        self.graph = self.segments = self._static = self._key = None
+        static = (src.clone(), tgt.clone())
         saved = self.snapshot()
         if self._cap_stream is None:
             # one warm-up and one capture stream for every captured shape: the
@@ -244,7 +350,7 @@ class TrainStep:
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(warmup):
-                self.eager(*self._static)
+                self.eager(*static, pos)
         torch.cuda.current_stream().wait_stream(s)
         self.restore(saved)
         del saved
@@ -264,7 +370,7 @@ class TrainStep:
             try:
                 with torch.cuda.stream(cap):
                     rec.begin()
-                    self.eager(*self._static)
+                    self.eager(*static, pos)
                     rec.end()
             except BaseException:
                 rec.abort()
@@ -272,21 +378,25 @@ class TrainStep:
             finally:
                 self.ddp.recorder = None
             torch.cuda.current_stream().wait_stream(cap)
-            self.segments = rec
-            self._register()
-            return True
+            self._register(None, rec, static, pos)
+            return
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, pool=self._pool, stream=self._cap_stream):
-            self.eager(*self._static)
-        self.graph = g
-        self._register()
-        return True
+            self.eager(*static, pos)
+        self._register(g, None, static, pos)
 
     # ------------------------------------------------------------------ shape cache
-    def _register(self) -> None:
-        """The just-captured step becomes the cache entry of its shape."""
-        self._key = (tuple(self._static[0].shape), tuple(self._static[1].shape))
-        self._graphs[self._key] = (self.graph, self.segments, self._static)
+    def _cache_key(self, src_shape, tgt_shape, pos: str) -> tuple:
+        """What a captured micro-batch bakes in: the batch shape, its position
+        in the update, the loss divisor (world * accum_steps, or 1 with the
+        global token mean) and where the label count comes from."""
+        return (tuple(src_shape), tuple(tgt_shape), pos, self.workers, self.global_mean)
+
+    def _register(self, graph, segments, static, pos: str) -> None:
+        """The just-captured micro-batch becomes the current cache entry."""
+        self.graph, self.segments, self._static, self._pos = graph, segments, static, pos
+        self._key = self._cache_key(static[0].shape, static[1].shape, pos)
+        self._graphs[self._key] = (graph, segments, static)
         self._graphs.move_to_end(self._key)
         self.graph_stats["captures"] += 1
 
@@ -294,32 +404,55 @@ class TrainStep:
     def cached_shapes(self) -> int:
         return len(self._graphs)
 
-    def _select(self, src: torch.Tensor, tgt: torch.Tensor) -> None:
-        """Make the captured step of this batch shape current: a cache hit,
-        or (bucketed) a capture of the new shape, evicting the least recently
-        used one when the cache is full. Every rank sees the same global-batch
-        shapes in the same order, so every rank captures and evicts alike."""
-        key = (tuple(src.shape), tuple(tgt.shape))
+    def _install(self, entries) -> None:
+        """Replace the cache by `entries` (none: the step runs eagerly)."""
+        self._graphs = OrderedDict(entries or ())
+        self.graph = self.segments = None
+        self._static = None
+        self._key = None
+        if self._graphs:  # the newest entry is current
+            key = next(reversed(self._graphs))
+            self.graph, self.segments, self._static = self._graphs[key]
+            self._key, self._pos = key, key[2]
+
+    def _select(self, src: torch.Tensor, tgt: torch.Tensor, pos: str = "only") -> None:
+        """Make the captured micro-batch of this batch shape and position
+        current: a cache hit, or (bucketed) a capture on the spot, evicting
+        the least recently used one when the cache is full. Every rank sees
+        the same global-batch shapes in the same order, so every rank
+        captures and evicts alike."""
+        key = self._cache_key(src.shape, tgt.shape, pos)
         if key == self._key:
             return
         ent = self._graphs.get(key)
         if ent is not None:
             self._graphs.move_to_end(key)
             self.graph, self.segments, self._static = ent
-            self._key = key
+            self._key, self._pos = key, pos
             return
         if not self.bucketed:
-            raise ValueError(f"captured step takes {tuple(self._static[0].shape)} / "
-                             f"{tuple(self._static[1].shape)} batches, got {tuple(src.shape)} / "
-                             f"{tuple(tgt.shape)}")
+            shapes = sorted({(k[0], k[1]) for k in self._graphs})
+            raise ValueError(f"captured step takes {' or '.join(f'{a} / {b}' for a, b in shapes)} "
+                             f"batches, got {tuple(src.shape)} / {tuple(tgt.shape)}")
         while len(self._graphs) >= max(1, self.graph_cache):
             self._graphs.popitem(last=False)
             self.graph_stats["evictions"] += 1
-        self.graph = self.segments = None
-        self._static = None
-        self._key = None
-        if not self.capture(src, tgt, warmup=1):
+        if self.capture_mode() == "0":
             raise RuntimeError("bucketed step: capture of a new batch shape failed")
+        self._capture_micro(src, tgt, pos, warmup=1)
+
+    def _replay(self, src: torch.Tensor, tgt: torch.Tensor, pos: str) -> None:
+        st = self._static
+        if st is None or pos != self._pos or src.shape != st[0].shape or tgt.shape != st[1].shape:
+            self._select(src, tgt, pos)
+            st = self._static
+        self.graph_stats["replays"] += 1
+        st[0].copy_(src, non_blocking=True)
+        st[1].copy_(tgt, non_blocking=True)
+        if self.segments is not None:
+            self.segments.replay()
+        else:
+            self.graph.replay()
 
     def choose_dp_mode(self, src: torch.Tensor, tgt: torch.Tensor, steps: int = 8,
                        rounds: int = 3, margin: float = 0.03) -> Dict[str, object]:
@@ -329,7 +462,8 @@ class TrainStep:
         and the eager step; and, where a comm thread exists
         (ddp.COMM_THREAD "auto"), both once more with the collectives issued
         by the host comm thread instead of the process group's own stream
-        handoff. Each arm is timed in interleaved rounds
+        handoff. With accum_steps > 1 every arm runs whole updates (the batch
+        repeated as each micro-batch). Each arm is timed in interleaved rounds
         (median per arm, MAX over ranks, so every rank takes the same
         decision) and, after its timed steps, the replicas must be bitwise
         equal (DataParallel.verify_replicas raises otherwise: an issue path
@@ -363,14 +497,16 @@ class TrainStep:
             return unmeasured(self.capture_mode())
         if not (ddp is not None and ddp.active and self.segments is not None) or not DP_AUTOSELECT:
             return unmeasured("seg" if self.segments is not None else self.capture_mode())
-        arms = {"seg": (self.segments, ddp._thread is not None)}
+        # an arm: the captured micro-batches of one update (cache entries)
+        arms = {"seg": (dict(self._graphs), ddp._thread is not None)}
         if auto_thread:
-            self.segments = None
+            self._install(None)
             ddp.use_thread(True)
             if self.capture(src, tgt):
-                arms["seg_thread"] = (self.segments, True)
+                arms["seg_thread"] = (dict(self._graphs), True)
             ddp.use_thread(False)
         saved = self.snapshot()
+        micro = [(src, tgt)] * self.accum_steps
         dev = self.model.device
 
         def timed(run) -> float:
@@ -387,13 +523,8 @@ class TrainStep:
             ddp.verify_replicas()  # the arm kept synchronous DP exact
             return dt
 
-        def seg_run(name):
-            segs, th = arms[name]
-
-            def run():
-                self.segments = segs
-                self(src, tgt)
-            return run, th
+        def run():
+            self.update(micro)
 
         # eager arms: the process group's handoff, and (auto) the comm thread
         eager_arms = {"0": False}
@@ -404,13 +535,12 @@ class TrainStep:
         for _ in range(rounds):
             for k in names:
                 if k in eager_arms:
-                    self.segments = None
+                    self._install(None)
                     ddp.use_thread(eager_arms[k])
-                    runs[k].append(timed(lambda: self.eager(src, tgt)))
                 else:
-                    run, th = seg_run(k)
-                    ddp.use_thread(th)  # (a captured graph keeps its own path)
-                    runs[k].append(timed(run))
+                    self._install(arms[k][0])
+                    ddp.use_thread(arms[k][1])  # (a captured graph keeps its own path)
+                runs[k].append(timed(run))
         # median per arm: one noisy round (box clock, host contention) does
         # not decide the mode for the whole run
         med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
@@ -422,20 +552,16 @@ class TrainStep:
         best_seg = min((k for k in names if k not in eager_arms), key=lambda k: ms[k])
         best_eager = min(eager_arms, key=lambda k: ms[k])
         if ms[best_eager] < ms[best_seg] * (1.0 - margin):
-            self.segments = None
-            self._static = None
+            self._install(None)
             th = eager_arms[best_eager]
             ddp.use_thread(th)
             mode = "0"
         else:
-            self.segments, th = arms[best_seg]
+            self._install(arms[best_seg][0])
+            th = arms[best_seg][1]
             ddp.use_thread(th)
             mode = "seg"
         arms.clear()  # the other captures' graphs are released
-        self._graphs.clear()
-        self._key = None
-        if self.segments is not None:
-            self._register()
         torch.cuda.synchronize()
         out = {"mode": mode, "comm_thread": th, "reason": "measured"}
         out.update({f"{k.replace('0', 'eager', 1) if k.startswith('0') else k}_ms": round(v * 1e3, 3)
@@ -444,17 +570,14 @@ class TrainStep:
         return out
 
     def __call__(self, src: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
+        if self.accum_steps != 1:
+            raise ValueError(f"a TrainStep with accum_steps={self.accum_steps} takes whole updates: "
+                             "update(micro_batches)")
         if self.opt.ema is not None:  # (a replayed graph runs no Python: checked here)
             self.opt.ema.check_not_swapped("training step")
         if not self.captured:
             return self.eager(src, tgt)
-        if src.shape != self._static[0].shape or tgt.shape != self._static[1].shape:
-            self._select(src, tgt)
-        self.graph_stats["replays"] += 1
-        self._static[0].copy_(src, non_blocking=True)
-        self._static[1].copy_(tgt, non_blocking=True)
-        if self.segments is not None:
-            self.segments.replay()
-        else:
-            self.graph.replay()
+        self._replay(src, tgt, "only")
         return self.last
+
+    step = __call__
