@@ -23,6 +23,7 @@ void def_attention(py::module_& m);
 void def_decode(py::module_& m);
 void def_layernorm(py::module_& m);
 void def_embedding(py::module_& m);
+void def_batch(py::module_& m);
 void def_fp8(py::module_& m);
 void def_loss(py::module_& m);
 void def_optimizer(py::module_& m);

@@ -8,6 +8,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   def_decode(m);
   def_layernorm(m);
   def_embedding(m);
+  def_batch(m);
   def_fp8(m);
   def_loss(m);
   def_optimizer(m);

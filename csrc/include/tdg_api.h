@@ -140,6 +140,17 @@ int tdg_transpose_grouped(const void* const* src, void* const* dst, int G, int R
 int tdg_ema(const float* p, float* e, long long n, long long* count, float decay, int warmup,
             int inc_count, const float* gstate, hipStream_t st);
 
+// --------------------------------------------------------------- batch.hip
+// out0 [B, L0] (nsides == 2: and out1 [B, L1]) = store rows idx[0, B), cut at
+// L and right-padded with 0; a side's store: int32 tokens (ntok words) and
+// int64 offsets [nrows + 1]; out64: int64 outputs, else int32; bad (or null):
+// counter of cut / out-of-range rows. -1: nsides outside [1, 2]; -2: B < 1;
+// -3: an L < 1; -4: an nrows < 0
+int tdg_gather_rows(int nsides, const int* idx, int B, int out64, const int* tok0,
+                    const long long* off0, int nrows0, long long ntok0, void* out0, int L0,
+                    const int* tok1, const long long* off1, int nrows1, long long ntok1,
+                    void* out1, int L1, unsigned* bad, hipStream_t st);
+
 // ------------------------------------ fp8_gemm.hip, fp8_wgrad.hip, fp8_quant.hip
 // afmt / cfmt / fmt: 0 e4m3, 1 e5m2; amax: a 2048-word slot (or slot table)
 int tdg_gemm_fp8(const void* A, const void* B, void* C, const float* bias, const float* sa,

@@ -122,6 +122,20 @@ class Settings:
     # replicas with one batch each (train/step.py TrainStep.update). An integer
     # in [1, 32]; not with dtype=fp8
     accum_steps: int = 1
+    # extension, off at 0: token-budget batches of data=text (data/text.py
+    # plan_token_batches). batch_tokens = N > 0 is the per-rank budget of
+    # processed positions per batch, rows_per_rank * (S + T - 1) with S the
+    # padded source and T - 1 the padded decoder-input length: the pairs are
+    # sorted by length and cut into batches of varying row count, each padded
+    # to a multiple of length_bucket (>= 1; graph_bucket and local_batch_size
+    # are not used in this mode). Label counts then differ a lot between
+    # batches, so loss_mode=global_mean is the sensible companion.
+    # corpus_on_device (with batch_tokens > 0 on a GPU): the tokenised corpus
+    # lives on the device and a batch is one gather launch
+    # (data/corpus.py); false assembles the same batches on the host
+    batch_tokens: int = 0
+    length_bucket: int = 8
+    corpus_on_device: bool = True
 
     def global_batch(self, world: int) -> int:
         return self.local_batch_size * world
@@ -167,6 +181,7 @@ def load_settings(path: Optional[str] = None, overrides: Optional[List[str]] = N
     if not (isinstance(s.ema_decay, (int, float)) and 0.0 <= float(s.ema_decay) < 1.0):
         raise ValueError(f"ema_decay must lie in [0, 1) (0: off), got {s.ema_decay!r}")
     check_accum_steps(s.accum_steps, s.dtype)
+    check_batch_tokens(s.batch_tokens, s.data, s.length_bucket)
     return s
 
 
@@ -181,4 +196,18 @@ def check_accum_steps(n: Any, dtype: str = "bf16") -> int:
     if n > 1 and dtype == "fp8":
         raise ValueError(f"accum_steps={n} with dtype=fp8 is not supported: the fp8 delayed scaling "
                          "assumes one forward/backward per optimizer update (use dtype=bf16)")
+    return n
+
+
+def check_batch_tokens(n: Any, data: str = "text", length_bucket: Any = 8) -> int:
+    """batch_tokens is an integer >= 0 (0: fixed local_batch_size batches) and
+    non-zero only with data=text; length_bucket is an integer >= 1;
+    ValueError otherwise."""
+    if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+        raise ValueError(f"batch_tokens must be an integer >= 0 (0: off), got {n!r}")
+    if isinstance(length_bucket, bool) or not isinstance(length_bucket, int) or length_bucket < 1:
+        raise ValueError(f"length_bucket must be an integer >= 1, got {length_bucket!r}")
+    if n > 0 and data != "text":
+        raise ValueError(f"batch_tokens={n} needs data=text (token-budget batches are cut from a "
+                         f"text corpus), got data={data!r}")
     return n

@@ -922,6 +922,50 @@ def check_trailing_padding() -> None:
                          "must be right-padded (attention masks keys by length)")
 
 
+def gather_rows(idx, tokens, offsets, outs, bad=None) -> None:
+    """One launch (batch.hip): outs[i] [B, L_i] (int64 or int32, one dtype) =
+    rows idx (int32 [B]) of side i's flat store -- tokens[i] int32, offsets[i]
+    int64 [n_rows + 1] -- cut at L_i and right-padded with PAD, for one or two
+    sides. A cut row or an id outside the store (written all-PAD) bumps `bad`
+    (int32 device word, or None). No allocation, no sync. An empty idx, an
+    L < 1 or another side count raise and launch nothing."""
+    C().gather_rows(idx, list(tokens), list(offsets), list(outs), bad)
+
+
+_GATHER_BAD: Dict[torch.device, torch.Tensor] = {}
+
+
+def gather_bad_counter(device) -> torch.Tensor:
+    """The device's bad-row counter word of gather_rows (int32 [1], zeroed)."""
+    dev = torch.device(device)
+    if dev.index is None:
+        dev = torch.device(dev.type, torch.cuda.current_device())
+    t = _GATHER_BAD.get(dev)
+    if t is None:
+        t = _GATHER_BAD[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
+    return t
+
+
+def gather_bad_rows(reset: bool = False) -> int:
+    """Rows gather_rows cut or found outside the store since the last reset.
+    Reads the device counters (a host sync): call at log points."""
+    n = 0
+    for t in _GATHER_BAD.values():
+        n += int(t.item())
+        if reset:
+            t.zero_()
+    return n
+
+
+def check_gather_rows() -> None:
+    """Raise if a batch gathered on the GPU asked for a row outside the corpus
+    or for fewer columns than a row holds (a batch-plan bug)."""
+    n = gather_bad_rows(reset=True)
+    if n:
+        raise ValueError(f"{n} gathered batch rows were longer than the batch's padded length or had "
+                         "an id outside the device corpus; the batch plan and the corpus disagree")
+
+
 def xent(logits, V, labels, ntok, workers, smoothing, row_loss, row_correct, write_grad=True):
     C().xent(logits, V, labels, ntok, workers, smoothing, row_loss, row_correct, write_grad)
 

@@ -24,7 +24,10 @@ broadcast with the optimizer state, validated in a second pass per epoch
 snapshot as `model_weights_ema`; with `accum_steps` = N > 1 gradient
 accumulation: an optimizer update takes N consecutive batches of the epoch
 (TrainStep.update), and steps, log points, fault injection and timings count
-updates.
+updates; with `batch_tokens` > 0 (data=text) length-sorted token-budget batches
+of varying row count (data/text.py), gathered on the device from a resident
+corpus (data/corpus.py) unless `corpus_on_device` is off, and `fill` and
+`real_tokens_per_s` (non-PAD positions) in the epoch line and record.
 
 Metric reads are the only host syncs: the device accumulators are summed over
 ranks (one small all-reduce) at log points, not every step.
@@ -42,7 +45,7 @@ import torch.distributed as dist
 
 from tensorflow_distributed_on_gke_amd.checkpoint import bundle
 from tensorflow_distributed_on_gke_amd.checkpoint.uploader import ModelUploader, make_storage
-from tensorflow_distributed_on_gke_amd.config import Settings, check_accum_steps
+from tensorflow_distributed_on_gke_amd.config import Settings, check_accum_steps, check_batch_tokens
 from tensorflow_distributed_on_gke_amd.data.synthetic import SyntheticPairs
 from tensorflow_distributed_on_gke_amd.models.layers import RunCtx
 from tensorflow_distributed_on_gke_amd.models.transformer import Transformer, model_config
@@ -87,6 +90,7 @@ class Trainer:
     def __post_init__(self):
         s, info = self.settings, self.info
         check_accum_steps(s.accum_steps, s.dtype)
+        check_batch_tokens(s.batch_tokens, s.data, s.length_bucket)
         if s.worker_count != info.world and info.chief:
             # the reference used worker_count both as expected size and loss
             # divisor; the runtime world size wins
@@ -128,12 +132,24 @@ class Trainer:
             st, tt = self.tokenizers
             # (hip_graph: batches padded to length buckets, one captured step each)
             bucket = s.graph_bucket if s.hip_graph and info.device.type == "cuda" else 1
+            train_kw, val_kw = {"bucket": bucket}, {}
+            if s.batch_tokens > 0:
+                # token-budget batches (data/text.py plan_token_batches): padded to
+                # length_bucket, eager or captured; training and validation alike
+                on_dev = s.corpus_on_device and info.device.type == "cuda"
+                train_kw = val_kw = dict(batch_tokens=s.batch_tokens, bucket=s.length_bucket,
+                                         corpus=info.device if on_dev else None)
+                if info.chief:
+                    self.log(f"token-budget batches: batch_tokens={s.batch_tokens} positions per rank, "
+                             f"length_bucket={s.length_bucket}, batches assembled on the "
+                             f"{'device' if on_dev else 'host'}; local_batch_size="
+                             f"{s.local_batch_size} is ignored")
             self.train_data = TextPairs(s.train_file, st, tt, s.local_batch_size, info.rank, info.world,
                                         seed=s.seed, shuffle_buffer=s.shuffle_buffer, max_len=s.max_len,
-                                        pin=info.device.type == "cuda", bucket=bucket)
+                                        pin=info.device.type == "cuda", **train_kw)
             self.val_data = TextPairs(s.validation_file or s.train_file, st, tt, s.local_batch_size,
                                       info.rank, info.world, seed=s.seed, shuffle=False,
-                                      max_len=s.max_len)
+                                      max_len=s.max_len, **val_kw)
             s.steps_per_epoch = self.train_data.steps_per_epoch  # one pass per epoch
             s.validation_steps = self.val_data.steps_per_epoch
         else:
@@ -149,6 +165,8 @@ class Trainer:
         self.global_step = 0
         self.timer = StepTimer(info.device)
         self.metrics = MetricsWriter(s.metrics_file if info.chief else None)
+        # token-budget batches: per epoch, fill and real tokens/s (fit())
+        self.token_history: List[Dict[str, float]] = []
 
     # ------------------------------------------------------------------ state
     @property
@@ -245,6 +263,8 @@ class Trainer:
         a = self._reduce(acc)
         if self.info.device.type == "cuda":
             K.check_trailing_padding()
+            if s.batch_tokens > 0:
+                K.check_gather_rows()
         n = max(float(a[2]), 1.0)
         return {"loss": float(a[0]) / n, "acc": float(a[1]) / n}
 
@@ -319,10 +339,15 @@ class Trainer:
             t0 = time.time()
             self.step_fn.accum.zero_()
             epoch_tokens = 0
+            real_tokens = 0  # token-budget batches: non-PAD positions, from the plan's lengths
             if N > 1:  # the epoch's own first batch (the previous one's tail is skipped)
                 self.train_data.seek(epoch * s.steps_per_epoch)
             for batch in range(steps):
-                micro = [self._to_dev(self.train_data.next()) for _ in range(N)]
+                micro = []
+                for _ in range(N):
+                    micro.append(self._to_dev(self.train_data.next()))
+                    if s.batch_tokens > 0:
+                        real_tokens += self.train_data.last_counts[0]
                 src, tgt = micro[0]
                 epoch_tokens += sum((a.shape[1] + b.shape[1] - 1) * a.shape[0] for a, b in micro) * info.world
                 if s.hip_graph and info.device.type == "cuda" and not captured \
@@ -360,6 +385,8 @@ class Trainer:
                 if batch % s.log_every == 0:
                     if info.device.type == "cuda":
                         K.check_trailing_padding()  # rows with interior PADs (device counter)
+                        if s.batch_tokens > 0:
+                            K.check_gather_rows()  # rows the device gather cut or could not find
                     a = self._reduce(self.step_fn.accum)
                     n = max(float(a[2]) / self._replicas, 1.0)
                     st = summarize(self.timer.drain())
@@ -395,13 +422,23 @@ class Trainer:
                             epoch_tokens / max(train_time, 1e-9))
             self.history.append(st)
             self.timer.drain()
-            self.metrics.write(kind="epoch", **st.__dict__, **ema_rec, **self._clip_record())
+            tok_rec = {}
+            if s.batch_tokens > 0:
+                tok_rec = {"real_tokens_per_s": real_tokens / max(train_time, 1e-9),
+                           "fill": real_tokens / max(epoch_tokens, 1)}
+                self.token_history.append(tok_rec)
+            self.metrics.write(kind="epoch", **st.__dict__, **ema_rec, **tok_rec, **self._clip_record())
             if info.chief:
                 self.log(f"Epoch {epoch + 1} Loss {train_loss:.4f} Accuracy {train_acc:.4f} "
                          f"Test Loss {val['loss']:.4f} Test Accuracy {val['acc']:.4f}")
                 if ema_val is not None:
                     self.log(f"EMA Test Loss {ema_val['loss']:.4f} Test Accuracy {ema_val['acc']:.4f}")
-                self.log(f"Time taken for 1 epoch: {dt:.2f} secs ({st.tokens_per_s:,.0f} tokens/s)\n")
+                if tok_rec:
+                    self.log(f"Time taken for 1 epoch: {dt:.2f} secs ({st.tokens_per_s:,.0f} tokens/s, "
+                             f"{tok_rec['real_tokens_per_s']:,.0f} real tokens/s, fill "
+                             f"{tok_rec['fill']:.3f})\n")
+                else:
+                    self.log(f"Time taken for 1 epoch: {dt:.2f} secs ({st.tokens_per_s:,.0f} tokens/s)\n")
             if info.world > 1:
                 self._quiet("epoch barrier")
                 dist.barrier()
