@@ -1,5 +1,6 @@
 // Decoding bindings: single-query attention over an indexed K/V cache and the
-// beam-search selection and sampling steps (decode.hip).
+// beam-search selection and sampling steps and the ensemble's probability
+// average (decode.hip).
 #include <algorithm>
 #include <cmath>
 
@@ -193,6 +194,53 @@ void sample_token(const Tensor& logits, int64_t V, const Tensor& score, const Te
   check_err(tdg_sample_token(&a, stream_of(logits)), "tdg sample_token");
 }
 
+// weights: the members' mixture weights, > 0 (the Python wrapper normalises
+// them to sum 1); the kernel gets their logarithms
+void ensemble_logprobs(const std::vector<Tensor>& logits, int64_t V,
+                       const std::vector<double>& weights, const Tensor& out) {
+  const int64_t M = (int64_t)logits.size();
+  TORCH_CHECK(M >= 1 && M <= tdg::ENSEMBLE_MAX, "ensemble_logprobs: 1 to ", tdg::ENSEMBLE_MAX,
+              " members, got ", M);
+  TORCH_CHECK((int64_t)weights.size() == M, "ensemble_logprobs: ", weights.size(), " weights for ",
+              M, " members");
+  TORCH_CHECK(V >= 1 && V <= 65536, "ensemble_logprobs: V must be in [1, 65536], got ", V);
+  check_bf16(out, "out");
+  TORCH_CHECK(out.dim() == 2 && out.stride(1) == 1 && out.size(1) >= V && out.size(1) % 8 == 0,
+              "out must be [R, >= V] with a multiple of 8 columns, rows contiguous");
+  const int64_t R = out.size(0), No = out.size(1), ldo = out.stride(0);
+  TORCH_CHECK(R < (1LL << 31) && ldo < (1LL << 31), "ensemble_logprobs: out too large");
+  TORCH_CHECK(ldo % 8 == 0 && (ldo >= No || R <= 1),
+              "ensemble_logprobs: out row stride must be a multiple of 8");
+  check_aligned(out, 16, "out");
+  check_extent(out, R, ldo, No, "out");
+  tdg::EnsembleArgs a{};
+  for (int64_t m = 0; m < M; ++m) {
+    const Tensor& x = logits[m];
+    check_bf16(x, "logits");
+    TORCH_CHECK(x.device() == out.device(), "ensemble_logprobs: members and out on one device");
+    TORCH_CHECK(x.dim() == 2 && x.size(0) == R && x.stride(1) == 1 && x.size(1) >= V,
+                "every member's logits must be [R, >= V], rows contiguous");
+    const int64_t ldl = x.stride(0);
+    TORCH_CHECK(ldl < (1LL << 31) && ldl % 8 == 0 && (ldl >= round8(V) || R <= 1),
+                "ensemble_logprobs: logits row stride must be a multiple of 8");
+    check_aligned(x, 16, "logits");
+    check_extent(x, R, ldl, round8(V), "logits");
+    TORCH_CHECK(std::isfinite(weights[m]) && weights[m] > 0 && std::isfinite(std::log(weights[m])),
+                "ensemble_logprobs: weights must be finite and > 0, got ", weights[m]);
+    a.x[m] = (const uint16_t*)x.data_ptr();
+    a.ldl[m] = (int)ldl;
+    a.logw[m] = (float)std::log(weights[m]);
+  }
+  a.out = (uint16_t*)out.data_ptr();
+  a.M = (int)M;
+  a.R = (int)R;
+  a.V = (int)V;
+  a.ldo = (int)ldo;
+  a.No = (int)No;
+  c10::DeviceGuard g(out.device());
+  check_err(tdg_ensemble_logprobs(&a, stream_of(out)), "tdg ensemble_logprobs");
+}
+
 }  // namespace
 
 void def_decode(py::module_& m) {
@@ -209,4 +257,6 @@ void def_decode(py::module_& m) {
         py::arg("fin"), py::arg("end_id"), py::arg("pad_id"), py::arg("temperature"),
         py::arg("top_k"), py::arg("top_p"), py::arg("seed"), py::arg("step"), py::arg("row_id"),
         py::arg("score_out"), py::arg("token"), py::arg("fin_out"));
+  m.def("ensemble_logprobs", &ensemble_logprobs, py::arg("logits"), py::arg("V"),
+        py::arg("weights"), py::arg("out"));
 }

@@ -62,4 +62,16 @@ struct SampleArgs {
   int R, V, ldl, end_id, pad_id;
 };
 
+// The ensemble's combine step: M members' logits -> the log of the weighted
+// mean of their probabilities, one row per hypothesis. The members ride in
+// the argument block by value: no pointer table on the device.
+constexpr int ENSEMBLE_MAX = 8;
+struct EnsembleArgs {
+  const uint16_t* x[ENSEMBLE_MAX];  // member m: bf16 [R, ldl[m]], the first V columns count
+  float logw[ENSEMBLE_MAX];         // log of the weights (> 0, sum 1)
+  int ldl[ENSEMBLE_MAX];
+  uint16_t* out;  // bf16 [R, ldo]: columns [0, V) written, [V, No) set to -inf
+  int M, R, V, ldo, No;
+};
+
 }  // namespace tdg

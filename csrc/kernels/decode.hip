@@ -1,6 +1,6 @@
 // Decoding kernels (gfx950): single-query attention over an indexed K/V cache
-// the beam-search selection step and the sampling step. Used by infer/beam.py
-// and infer/sample.py.
+// the beam-search selection step, the sampling step and the ensemble's
+// probability average. Used by infer/step.py, infer/beam.py and infer/sample.py.
 //
 // decode_attn: M = 1 per (row, head), so there is no matrix to feed the MFMA
 // units: the kernel is a stream over the keys. One wave per (row, head), four
@@ -24,6 +24,13 @@
 // to 8192 columns stays in registers, a longer one, at most 128 KiB, is
 // re-read from L2), the draw is a Gumbel-max over the kept set: no sort, no
 // prefix sums, every reduction in a fixed order.
+//
+// ensemble_logprobs: one workgroup per row. Pass 1 streams the row of every
+// member once, each thread keeping an online (max, sum) pair per member; the
+// pairs are reduced over the workgroup in a fixed order (no atomics). Pass 2
+// re-reads the rows (at most 8 x 128 KiB, from L2) and stores the log of the
+// weighted mean probability, 16 bytes at a time. The members' pointers ride
+// in the argument block: nothing to upload before a launch.
 #include "tdg_api.h"
 #include "tdg_common.h"
 
@@ -490,6 +497,109 @@ __global__ __launch_bounds__(256) void sample_token_kernel(const SampleArgs a) {
   }
 }
 
+// ---------------------------------------------------------------- ensemble_logprobs
+template <int M>
+__global__ __launch_bounds__(256) void ensemble_logprobs_kernel(const EnsembleArgs a) {
+  __shared__ float red[ENSEMBLE_MAX][4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = blockIdx.x, V = a.V;
+  const uint16_t* x[M];
+#pragma unroll
+  for (int m = 0; m < M; ++m) x[m] = a.x[m] + (long long)r * a.ldl[m];
+
+  // pass 1: per member the row's logsumexp over its finite logits
+  float mx[M], sum[M];
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    mx[m] = -INFINITY;
+    sum[m] = 0.f;
+  }
+  for (int c = tid * 8; c < V; c += 2048) {
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      float f[8];
+      unpack8(*reinterpret_cast<const uint4*>(x[m] + c), f);
+      float cm = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        if (!(c + i < V && f[i] > -INFINITY)) f[i] = -INFINITY;  // padding, -inf, NaN: probability 0
+        cm = fmaxf(cm, f[i]);
+      }
+      if (cm > mx[m]) {  // one rescale per chunk of 8
+        sum[m] *= __expf(mx[m] - cm);
+        mx[m] = cm;
+      }
+      if (mx[m] > -INFINITY) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sum[m] += __expf(f[i] - mx[m]);
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    const float w = wave_max(mx[m]);
+    if (lane == 0) red[m][wave] = w;
+  }
+  __syncthreads();
+  float gm[M];
+#pragma unroll
+  for (int m = 0; m < M; ++m) gm[m] = fmaxf(fmaxf(red[m][0], red[m][1]), fmaxf(red[m][2], red[m][3]));
+  __syncthreads();
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    const float w = wave_sum(mx[m] > -INFINITY ? sum[m] * __expf(mx[m] - gm[m]) : 0.f);
+    if (lane == 0) red[m][wave] = w;
+  }
+  __syncthreads();
+  // off[m] = log w_m - lse_m; -inf: member m has no finite logit in this row
+  float off[M];
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    const float tot = (red[m][0] + red[m][1]) + (red[m][2] + red[m][3]);
+    off[m] = gm[m] > -INFINITY ? a.logw[m] - (gm[m] + logf(tot)) : -INFINITY;
+  }
+
+  // pass 2: out = log sum_m exp(x_m + off_m); the columns [V, No) get -inf
+  uint16_t* const orow = a.out + (long long)r * a.ldo;
+  for (int c = tid * 8; c < a.No; c += 2048) {
+    float am[M][8], o[8];
+    if (c < V) {
+#pragma unroll
+      for (int m = 0; m < M; ++m) {
+        unpack8(*reinterpret_cast<const uint4*>(x[m] + c), am[m]);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          am[m][i] = (c + i < V && am[m][i] > -INFINITY) ? am[m][i] + off[m] : -INFINITY;
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        float top = am[0][i];
+#pragma unroll
+        for (int m = 1; m < M; ++m) top = fmaxf(top, am[m][i]);
+        float s = 0.f;
+        if (top > -INFINITY) {
+#pragma unroll
+          for (int m = 0; m < M; ++m) s += __expf(am[m][i] - top);
+        }
+        o[i] = top > -INFINITY ? top + logf(s) : -INFINITY;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o[i] = -INFINITY;
+    }
+    uint4 w;
+    w.x = pack2bf(o[0], o[1]);
+    w.y = pack2bf(o[2], o[3]);
+    w.z = pack2bf(o[4], o[5]);
+    w.w = pack2bf(o[6], o[7]);
+    *reinterpret_cast<uint4*>(orow + c) = w;
+  }
+}
+
+template <int M>
+static void launch_ensemble(const EnsembleArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(ensemble_logprobs_kernel<M>, dim3(a.R), dim3(256), 0, st, a);
+}
+
 }  // namespace tdg
 
 extern "C" {
@@ -548,6 +658,28 @@ int tdg_sample_token(const tdg::SampleArgs* a, hipStream_t st) {
     hipLaunchKernelGGL(tdg::sample_token_kernel<4>, grid, block, 0, st, *a);
   else
     hipLaunchKernelGGL(tdg::sample_token_kernel<0>, grid, block, 0, st, *a);
+  return 0;
+}
+
+// The log of the weighted mean of M members' next-token probabilities
+// (tdg_decode.h EnsembleArgs), a workgroup per row: out[r, v] = log sum_m
+// w_m softmax(x_m[r])[v] in f32, rounded to bf16; a NaN or -inf logit has
+// probability 0, a member's row without a finite logit none at all, a row no
+// member has a finite logit in is all -inf, as are the columns [V, No).
+// ldl % 8 == 0, ldo % 8 == 0, No % 8 == 0, 16-byte aligned rows.
+int tdg_ensemble_logprobs(const tdg::EnsembleArgs* a, hipStream_t st) {
+  if (a->M < 1 || a->M > tdg::ENSEMBLE_MAX || a->V < 1 || a->V > 65536) return -1;
+  if (a->R <= 0) return 0;
+  switch (a->M) {
+    case 1: tdg::launch_ensemble<1>(*a, st); break;
+    case 2: tdg::launch_ensemble<2>(*a, st); break;
+    case 3: tdg::launch_ensemble<3>(*a, st); break;
+    case 4: tdg::launch_ensemble<4>(*a, st); break;
+    case 5: tdg::launch_ensemble<5>(*a, st); break;
+    case 6: tdg::launch_ensemble<6>(*a, st); break;
+    case 7: tdg::launch_ensemble<7>(*a, st); break;
+    default: tdg::launch_ensemble<8>(*a, st); break;
+  }
   return 0;
 }
 

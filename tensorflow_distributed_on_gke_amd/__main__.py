@@ -1,7 +1,8 @@
 """Command line entry point.
 
     python -m tensorflow_distributed_on_gke_amd train [--config FILE] [--set key=value ...] [--nproc N]
-    python -m tensorflow_distributed_on_gke_amd test  --weights PREFIX [--ema] [--sentence TEXT ...] [--beam N]
+    python -m tensorflow_distributed_on_gke_amd test  --weights PREFIX [PREFIX ...] [--ensemble-weights W ...]
+            [--ema] [--sentence TEXT ...] [--beam N]
             [--sample N --temperature T --top-k K --top-p P --seed S] [--input FILE --output FILE [--batch N]]
     python -m tensorflow_distributed_on_gke_amd average --inputs PREFIX PREFIX ... --output PREFIX
     python -m tensorflow_distributed_on_gke_amd heartbeat --port 3479
@@ -18,7 +19,10 @@ search with --beam N --length-penalty ALPHA, or --sample N translations drawn
 per sentence); with --input / --output it translates a file, one sentence per
 line, to source<TAB>hypothesis<TAB>score lines; --ema decodes from the
 averaged weights a run with `ema_decay` wrote next to the snapshot
-(`<weights>_ema`).
+(`<weights>_ema`). Several --weights prefixes decode as an ensemble
+(infer/ensemble.py): one model per prefix, all built from the same settings,
+their next-token probabilities averaged with --ensemble-weights (default:
+equal) at every step; --ema then applies to every prefix.
 `average` is checkpoint averaging: the mean of several weight bundles (float64
 on the host) as one f32 bundle `test --weights` and `warm_start` load.
 """
@@ -97,16 +101,24 @@ def cmd_test(args) -> int:
         tok = SimpleNamespace(pt=pt, en=en)
     else:
         tok = ByteTokenizer(min(settings.src_vocab, settings.tgt_vocab))
-    model = build_model(settings, dev)
-    if args.weights:
-        prefix = bundle.resolve_prefix(args.weights)
-        if args.ema:
-            prefix += bundle.EMA_SUFFIX
-            if not os.path.exists(prefix + ".index"):
-                raise FileNotFoundError(f"test --ema: no averaged weights at {prefix} (written next to a "
-                                        "snapshot by a run with ema_decay > 0)")
-        bundle.load_weights(model.store, prefix)
-    tester = Tester(tok, model)
+    models = []
+    for w in args.weights or [None]:
+        model = build_model(settings, dev)
+        if w:
+            prefix = bundle.resolve_prefix(w)
+            if args.ema:
+                prefix += bundle.EMA_SUFFIX
+                if not os.path.exists(prefix + ".index"):
+                    raise FileNotFoundError(f"test --ema: no averaged weights at {prefix} (written next to "
+                                            "a snapshot by a run with ema_decay > 0)")
+            bundle.load_weights(model.store, prefix)
+        models.append(model)
+    if len(models) > 1:
+        from tensorflow_distributed_on_gke_amd.infer.ensemble import Ensemble
+
+        tester = Tester(tok, Ensemble(models, args.ensemble_weights))
+    else:
+        tester = Tester(tok, models[0])
     mode = dict(beam=args.beam, alpha=args.length_penalty, sample=args.sample,
                 temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
     if args.input:
@@ -161,7 +173,10 @@ def main(argv=None) -> int:
     t.add_argument("--heartbeat-port", type=int, default=3479)
     t.add_argument("--master-port", type=int, default=int(os.environ.get("MASTER_PORT", 3480)))
     e = sub.add_parser("test", parents=[common])
-    e.add_argument("--weights", default=None, help="weights prefix or directory")
+    e.add_argument("--weights", nargs="+", default=None, metavar="PREFIX",
+                   help="weights prefix or directory; several (at most 8) decode as an ensemble")
+    e.add_argument("--ensemble-weights", nargs="+", type=float, default=None, metavar="W",
+                   help="one positive mixture weight per --weights prefix (default: equal)")
     e.add_argument("--ema", action="store_true",
                    help="load the averaged weights saved next to --weights (<prefix>_ema)")
     e.add_argument("--sentence", action="append", default=None)
@@ -189,6 +204,13 @@ def main(argv=None) -> int:
     if args.cmd == "test":
         if args.ema and not args.weights:
             ap.error("test: --ema needs --weights")
+        if args.weights and len(args.weights) > 8:
+            ap.error("test: an ensemble has at most 8 members")
+        if args.ensemble_weights is not None:
+            if len(args.ensemble_weights) != len(args.weights or []):
+                ap.error("test: --ensemble-weights needs one value per --weights prefix")
+            if not all(0.0 < w < float("inf") for w in args.ensemble_weights):
+                ap.error("test: --ensemble-weights must be finite and > 0")
         if (args.input is None) != (args.output is None) or (args.input and args.sentence):
             ap.error("test: --input and --output go together, without --sentence")
         if args.beam > 1 and args.sample > 0:

@@ -1,8 +1,9 @@
 """Beam-search decoding on the single-query KV-cache attention kernel.
 
 Each of the B sentences keeps `beam` hypotheses, so the decoder runs on
-R = B * beam rows, one new token per row and step. Three things keep a step
-free of copies (csrc/kernels/decode.hip, docs/ARCHITECTURE.md "Inference"):
+R = B * beam rows, one new token per row and step (infer/step.py holds the
+model's side of it). Three things keep a step free of copies
+(csrc/kernels/decode.hip, docs/ARCHITECTURE.md "Inference"):
 
 * the ancestry table: one int32 [R, Tmax] table, shared by all layers, says
   for every live hypothesis and position which cache row holds that
@@ -17,12 +18,12 @@ step instead (no ancestry table); it gives bitwise the same result.
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Tuple, Union
 
 import torch
 
-from tensorflow_distributed_on_gke_amd.infer.greedy import _add_ln, _linear
-from tensorflow_distributed_on_gke_amd.models.layers import CrossKVFn, KVGrad, RunCtx
+from tensorflow_distributed_on_gke_amd.infer.ensemble import Ensemble, members
+from tensorflow_distributed_on_gke_amd.infer.step import DecoderStep
 from tensorflow_distributed_on_gke_amd.models.transformer import PAD_ID, Transformer, seq_lengths
 from tensorflow_distributed_on_gke_amd.ops import kernels as K
 
@@ -33,8 +34,8 @@ def length_penalty(length: torch.Tensor, alpha: float) -> torch.Tensor:
 
 
 @torch.no_grad()
-def beam_search(model: Transformer, src: torch.Tensor, start: int, end: int, beam: int = 4,
-                max_length: int = 20, alpha: float = 0.6, reorder: str = "index"
+def beam_search(model: Union[Transformer, Ensemble], src: torch.Tensor, start: int, end: int,
+                beam: int = 4, max_length: int = 20, alpha: float = 0.6, reorder: str = "index"
                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """src int64 [B, S] -> (tokens int64 [B, 1 + n], scores f32 [B],
     all_tokens int64 [B, beam, 1 + n], all_scores f32 [B, beam]).
@@ -44,32 +45,31 @@ def beam_search(model: Transformer, src: torch.Tensor, start: int, end: int, bea
     descending score, -inf marking a slot that never held one. `tokens` /
     `scores` are the hypothesis that maximises score / ((5 + len) / 6) **
     alpha, len counting the generated tokens including [END]; ended or not,
-    all are ranked alike."""
+    all are ranked alike.
+
+    `model` may be an `Ensemble` (infer/ensemble.py): its members run on the
+    same rows, one `DecoderStep` each, sharing the ancestry table, and the
+    candidates are scored by the log of the weighted mean of their
+    probabilities (`ops.kernels.ensemble_logprobs`, bf16 on the GPU: the
+    scores are those of the rounded, renormalised mixture). One member skips
+    the combine step and is bitwise that model."""
     if reorder not in ("index", "copy"):
         raise ValueError(f"reorder must be 'index' or 'copy', got {reorder!r}")
     if not 1 <= beam <= 8:
         raise ValueError(f"beam must be in [1, 8], got {beam}")
-    m = model
-    cfg = m.cfg
-    dev = m.device
+    models, weights = members(model)
+    cfg = models[0].cfg
+    dev = models[0].device
     src = src.to(dev)
     B = src.shape[0]
     R = B * beam
-    d, H = cfg.d_model, cfg.heads
-    hd = d // H
     V = cfg.tgt_vocab
-    scale = 1.0 / (hd ** 0.5)
-    if max_length + 1 > cfg.max_tgt_len:
-        raise ValueError(f"max_length {max_length} + 1 > positional table {cfg.max_tgt_len}")
-    rt = RunCtx(training=False, store=None)
+    for m in models:
+        if max_length + 1 > m.cfg.max_tgt_len:
+            raise ValueError(f"max_length {max_length} + 1 > positional table {m.cfg.max_tgt_len}")
     src_len = seq_lengths(src)
-    enc = m.encode(src, src_len, rt)
-    S = enc.shape[1]
-    kv_all = CrossKVFn.apply(enc, m.cross_kv.w, m.cross_kv.b, KVGrad(), rt).contiguous()
-    act = m.act_dtype
+    steps = [DecoderStep(m, src, src_len, R, max_length) for m in models]
     Tm = max_length + 1
-    kcache = [torch.zeros(R, Tm, H, hd, dtype=act, device=dev) for _ in m.dec_layers]
-    vcache = [torch.zeros(R, Tm, H, hd, dtype=act, device=dev) for _ in m.dec_layers]
     rows = torch.arange(R, dtype=torch.int32, device=dev)
     row_map = torch.div(rows, beam, rounding_mode="floor").to(torch.int32)
     cross_len = src_len[row_map.long()].to(torch.int32).contiguous()
@@ -87,33 +87,17 @@ def beam_search(model: Transformer, src: torch.Tensor, start: int, end: int, bea
     hist = torch.full((R, 1), start, dtype=torch.int64, device=dev)
     tok = hist[:, 0]
     for t in range(max_length):
-        if dev.type == "cuda":
-            x2 = K.embed_fwd(tok.view(R, 1).contiguous(), m.dec_emb.compute, m.pe_tgt[t:], d ** 0.5,
-                             0.0, 0, None, 0).view(R, d)
-        else:
-            x2 = m.dec_emb.master[tok] * (d ** 0.5) + m.pe_tgt[t].view(1, d)
         klen = torch.full((R,), t + 1, dtype=torch.int32, device=dev)
-        for li, layer in enumerate(m.dec_layers):
-            qkv = _linear(x2, layer.qkv1).view(R, 3, H, hd)
-            o = K.decode_attn(qkv[:, 0], kcache[li], vcache[li], klen, scale, anc=anc,
-                              k_new=qkv[:, 1], v_new=qkv[:, 2])
-            y = _add_ln(x2, _linear(o.reshape(R, d), layer.o1), layer.ln1)
-            q2 = _linear(y, layer.q2).view(R, H, hd)
-            kv5 = kv_all[:, :, li * 2 * d:(li + 1) * 2 * d].view(B, S, 2, H, hd)
-            o2 = K.decode_attn(q2, kv5[:, :, 0], kv5[:, :, 1], cross_len, scale, row_map=row_map)
-            y2 = _add_ln(y, _linear(o2.reshape(R, d), layer.o2), layer.ln2)
-            f = _linear(_linear(y2, layer.ff1, relu=True), layer.ff2)
-            x2 = _add_ln(y2, f, layer.ln3)
-        lg = m.project(x2.view(R, 1, d))
+        lgs = [st.logits(tok, t, klen, cross_len, row_map=row_map, anc=anc) for st in steps]
+        lg = lgs[0] if len(lgs) == 1 else K.ensemble_logprobs(lgs, V, weights)
         score, parent, token, fin_new, new_anc = K.beam_topk(lg, V, score, fin, beam, end, PAD_ID,
                                                              anc=anc, t=t, anc_out=nxt_anc)
         par = parent.long()
         if index:
             anc, nxt_anc = new_anc, anc
         elif t + 1 < max_length:
-            for li in range(len(m.dec_layers)):
-                kcache[li] = kcache[li].index_select(0, par)
-                vcache[li] = vcache[li].index_select(0, par)
+            for st in steps:
+                st.gather(par)
         tok = token.long()
         length = length[par] + (fin[par] == 0).long()
         hist = torch.cat([hist[par], tok.view(R, 1)], dim=1)

@@ -18,47 +18,35 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
-from tensorflow_distributed_on_gke_amd.models.layers import (LN_EPS, CrossKVFn, EmbedFn, KVGrad,
-                                                             RunCtx, _ref_attn_fwd)
+from tensorflow_distributed_on_gke_amd.infer.ensemble import Ensemble, members
+from tensorflow_distributed_on_gke_amd.infer.step import DecoderStep
+from tensorflow_distributed_on_gke_amd.models.layers import CrossKVFn, EmbedFn, KVGrad, RunCtx
 from tensorflow_distributed_on_gke_amd.models.transformer import PAD_ID, Transformer, seq_lengths
-from tensorflow_distributed_on_gke_amd.ops import kernels as K
-
-
-# --------------------------------------------------------------- single-token ops (GPU kernels / CPU f32)
-def _linear(x2, dense, relu=False):
-    if x2.is_cuda:
-        return K.linear_fwd(x2.contiguous(), dense.w.compute, dense.b.master, relu=relu)
-    y = x2 @ dense.w.master.t() + dense.b.master
-    return torch.relu(y) if relu else y
-
-
-def _add_ln(x, s, ln):
-    if x.is_cuda:
-        return K.ln_fwd(x.contiguous(), s.contiguous(), ln.gamma.master, ln.beta.master, 0.0, 0, None, 0,
-                        save=False)[0]
-    return torch.nn.functional.layer_norm(x + s, (x.shape[-1],), ln.gamma.master, ln.beta.master, LN_EPS)
-
-
-def _attend(q, k, v, kv_len, scale):
-    if q.is_cuda:
-        return K.attn_fwd(q, k, v, kv_len, scale, False)[0]
-    return _ref_attn_fwd(q, k, v, kv_len, False, scale)[0]
 
 
 class Tester:
     __test__ = False  # not a pytest class
 
-    def __init__(self, tokenizers, transformer: Transformer):
+    def __init__(self, tokenizers, transformer: Union[Transformer, Ensemble]):
         """`tokenizers` has `.pt` (source) and `.en` (target) tokenizers, as
-        the reference's; a single tokenizer object is used for both."""
+        the reference's; a single tokenizer object is used for both.
+        `transformer` is one model or an `Ensemble` (infer/ensemble.py) of
+        several, decoded together."""
         self.src_tok = getattr(tokenizers, "pt", tokenizers)
         self.tgt_tok = getattr(tokenizers, "en", tokenizers)
         self.model = transformer
 
+    def _single(self, what: str) -> Transformer:
+        """The one model `what` runs on: an ensemble has no such path."""
+        if isinstance(self.model, Ensemble):
+            raise ValueError(f"{what} decodes one model; an ensemble decodes with the K/V cache "
+                             "(beam search or sampling)")
+        return self.model
+
     @torch.no_grad()
     def greedy(self, src: torch.Tensor, max_length: int = 20) -> torch.Tensor:
         """src int64 [B, S] -> int64 [B, 1 + n] ([START] + generated ids)."""
-        m = self.model
+        m = self._single("greedy")
         dev = m.device
         src = src.to(dev)
         start, end = self.tgt_tok.start_end()
@@ -91,48 +79,18 @@ class Tester:
         runs the decoder on the ONE new token (O(T) work per step instead of
         the reference's full re-forward, tester.py:30-42). Same output as
         `greedy` up to floating-point summation order."""
-        m = self.model
-        cfg = m.cfg
+        m = self._single("greedy_cached")
         dev = m.device
         src = src.to(dev)
         start, end = self.tgt_tok.start_end()
         B = src.shape[0]
-        d, H = cfg.d_model, cfg.heads
-        hd = d // H
-        scale = 1.0 / (hd ** 0.5)
-        rt = RunCtx(training=False, store=None)
         src_len = seq_lengths(src)
-        enc = m.encode(src, src_len, rt)
-        S = enc.shape[1]
-        kv_all = CrossKVFn.apply(enc, m.cross_kv.w, m.cross_kv.b, KVGrad(), rt).contiguous()
-        act = m.act_dtype
-        Tm = max_length + 1
-        kcache = [torch.zeros(B, Tm, H, hd, dtype=act, device=dev) for _ in m.dec_layers]
-        vcache = [torch.zeros(B, Tm, H, hd, dtype=act, device=dev) for _ in m.dec_layers]
+        step = DecoderStep(m, src, src_len, B, max_length, single_query=False)
         out = torch.full((B, 1), start, dtype=torch.int64, device=dev)
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         for t in range(max_length):
-            tok = out[:, -1:]
-            if dev.type == "cuda":
-                x = K.embed_fwd(tok.contiguous(), m.dec_emb.compute, m.pe_tgt[t:], d ** 0.5, 0.0, 0,
-                                None, 0)
-            else:
-                x = m.dec_emb.master[tok] * (d ** 0.5) + m.pe_tgt[t].view(1, 1, d)
-            x2 = x.reshape(B, d)
             klen = torch.full((B,), t + 1, dtype=torch.int32, device=dev)
-            for li, layer in enumerate(m.dec_layers):
-                qkv = _linear(x2, layer.qkv1).view(B, 1, 3, H, hd)
-                kcache[li][:, t] = qkv[:, 0, 1]
-                vcache[li][:, t] = qkv[:, 0, 2]
-                o = _attend(qkv[:, :, 0], kcache[li][:, : t + 1], vcache[li][:, : t + 1], klen, scale)
-                y = _add_ln(x2, _linear(o.reshape(B, d), layer.o1), layer.ln1)
-                q2 = _linear(y, layer.q2).view(B, 1, H, hd)
-                kv5 = kv_all[:, :, li * 2 * d:(li + 1) * 2 * d].view(B, S, 2, H, hd)
-                o2 = _attend(q2, kv5[:, :, 0], kv5[:, :, 1], src_len, scale)
-                y2 = _add_ln(y, _linear(o2.reshape(B, d), layer.o2), layer.ln2)
-                f = _linear(_linear(y2, layer.ff1, relu=True), layer.ff2)
-                x2 = _add_ln(y2, f, layer.ln3)
-            lg = m.project(x2.view(B, 1, d))[:, : cfg.tgt_vocab].float()
+            lg = step.logits(out[:, -1], t, klen, src_len)[:, : m.cfg.tgt_vocab].float()
             nxt = lg.argmax(dim=-1)
             nxt = torch.where(done, torch.full_like(nxt, PAD_ID), nxt)
             out = torch.cat([out, nxt.view(B, 1)], dim=1)
@@ -143,7 +101,8 @@ class Tester:
 
     @torch.no_grad()
     def attention_weights(self, src: torch.Tensor, tgt_in: torch.Tensor) -> Dict[str, torch.Tensor]:
-        m = self.model
+        """The decoder's attention maps; of an ensemble, its first member's."""
+        m = members(self.model)[0][0]
         rt = RunCtx(training=False, store=None, attn_maps={})
         m.features(src.to(m.device), tgt_in.to(m.device), rt)
         out = {}
@@ -158,12 +117,18 @@ class Tester:
                ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """src int64 [B, S] -> (tokens int64 [B, n, 1 + len] on the CPU, scores
         f32 [B, n] or None): greedy (n = 1, no scores), beam search (beam > 1:
-        n = 1, the best hypothesis) or `sample` draws per sentence."""
+        n = 1, the best hypothesis) or `sample` draws per sentence. An
+        ensemble decodes on the K/V cache only (`kv_cache=False` is an error),
+        and its greedy mode is beam search of width 1 with alpha 0, whose
+        score is returned."""
         if sample < 0:
             raise ValueError(f"sample must be >= 0, got {sample}")
         if sample > 0 and beam > 1:
             raise ValueError("beam > 1 and sample > 0 exclude each other")
         start, end = self.tgt_tok.start_end()
+        ensemble = isinstance(self.model, Ensemble)
+        if ensemble and not kv_cache:
+            raise ValueError("an ensemble decodes with the K/V cache: kv_cache=False is not supported")
         if sample > 0:
             from tensorflow_distributed_on_gke_amd.infer.sample import sample_search
 
@@ -171,11 +136,11 @@ class Tester:
                                            temperature=temperature, top_k=top_k, top_p=top_p,
                                            seed=seed, row_id0=row_id0)
             return tokens.cpu(), scores.cpu()
-        if beam > 1:
+        if beam > 1 or ensemble:
             from tensorflow_distributed_on_gke_amd.infer.beam import beam_search
 
             tokens, scores = beam_search(self.model, src, start, end, beam=beam, max_length=max_length,
-                                         alpha=alpha)[:2]
+                                         alpha=alpha if beam > 1 else 0.0)[:2]
             return tokens.cpu().unsqueeze(1), scores.cpu().unsqueeze(1)
         out = (self.greedy_cached if kv_cache else self.greedy)(src, max_length).cpu()
         return out.unsqueeze(1), None
@@ -184,10 +149,14 @@ class Tester:
     def score(self, src: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
         """Teacher-forced f32 log-probability [B] of tokens int64 [B, 1 + len]
         ([START] first): the sum over the generated tokens up to and including
-        the first [END]."""
+        the first [END]. Of an ensemble: the log of the weighted mean of the
+        members' probabilities, token by token."""
         _, end = self.tgt_tok.start_end()
         tokens = tokens.to(self.model.device)
-        lp = torch.log_softmax(self.model.logits(src.to(self.model.device), tokens[:, :-1]), dim=-1)
+        if isinstance(self.model, Ensemble):
+            lp = self.model.log_probs(src.to(self.model.device), tokens[:, :-1])
+        else:
+            lp = torch.log_softmax(self.model.logits(src.to(self.model.device), tokens[:, :-1]), dim=-1)
         tok_lp = lp.gather(2, tokens[:, 1:].unsqueeze(-1)).squeeze(-1)
         after_end = (tokens[:, 1:] == end).long().cumsum(dim=1) - (tokens[:, 1:] == end).long() > 0
         return tok_lp.masked_fill(after_end, 0.0).sum(dim=1).cpu()

@@ -695,6 +695,57 @@ def sample_token(logits, V: int, score, fin, end_id: int, pad_id: int, temperatu
     return out, token.to(torch.int32), (off | (token == end_id)).to(torch.int32)
 
 
+ENSEMBLE_MAX = 8
+
+
+def ensemble_logprobs(logits_list, V: int, weights=None, out=None):
+    """The log of the weighted mean of M members' next-token probabilities.
+
+    logits_list: 1 to 8 tensors [R, >= V] (only the first V columns count; a
+    NaN or -inf logit has probability 0), weights: one positive number per
+    member (default uniform), normalised here to sum 1. With lse_m[r] =
+    logsumexp_v x_m[r, v] and a_m = x_m - lse_m + log w_m (-inf throughout a
+    member's row without a finite logit), out[r, v] = logsumexp_m a_m[r, v]; a
+    row no member has a finite logit in is all -inf, as are the columns from
+    V on. Returns `out`, [R, multiple of 8 >= V] (default: V rounded up).
+    GPU: bf16 members, each with its own row stride (a multiple of 8, rows
+    16-byte aligned), f32 arithmetic, bf16 output: the rounded mixture, which
+    the selection kernels renormalise (csrc/kernels/decode.hip). CPU: the same
+    definition in f32, unrounded."""
+    M = len(logits_list)
+    if not 1 <= M <= ENSEMBLE_MAX:
+        raise RuntimeError(f"ensemble_logprobs: {M} members outside [1, {ENSEMBLE_MAX}]")
+    if not 1 <= V <= 65536:
+        raise RuntimeError(f"ensemble_logprobs: V {V} outside [1, 65536]")
+    w = [1.0] * M if weights is None else [float(x) for x in weights]
+    if len(w) != M or not all(0.0 < x < float("inf") for x in w):
+        raise RuntimeError(f"ensemble_logprobs: needs {M} finite weights > 0, got {w}")
+    total = math.fsum(w)
+    w = [x / total for x in w]
+    first = logits_list[0]
+    R = first.shape[0]
+    if first.is_cuda:
+        if out is None:
+            out = torch.empty(R, (V + 7) // 8 * 8, dtype=torch.bfloat16, device=first.device)
+        C().ensemble_logprobs(list(logits_list), V, w, out)
+        return out
+    ninf = float("-inf")
+    rows = []
+    for x, wm in zip(logits_list, w):
+        x = x[:, :V].float()
+        x = torch.where(x > ninf, x, torch.full_like(x, ninf))  # NaN too
+        lse = torch.logsumexp(x, dim=1, keepdim=True)
+        rows.append(torch.where(lse > ninf, x - lse + math.log(wm), torch.full_like(x, ninf)))
+    mix = torch.logsumexp(torch.stack(rows), dim=0)
+    if out is None:
+        out = torch.empty(R, (V + 7) // 8 * 8, dtype=torch.float32)
+    if out.shape[0] != R or out.shape[1] < V:
+        raise RuntimeError(f"ensemble_logprobs: out {tuple(out.shape)} too small for [{R}, {V}]")
+    out[:, :V] = mix
+    out[:, V:] = ninf
+    return out
+
+
 # ------------------------------------------------------------------ layernorm
 def ln_fwd(x, s, gamma, beta, p, seed, ctr, site, eps=1e-6, save=True, y8=None, s8=None,
            amax8=None, kbits=None):
