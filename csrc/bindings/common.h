@@ -26,6 +26,7 @@ void def_embedding(py::module_& m);
 void def_batch(py::module_& m);
 void def_fp8(py::module_& m);
 void def_loss(py::module_& m);
+void def_distill(py::module_& m);
 void def_optimizer(py::module_& m);
 void def_ema(py::module_& m);
 void def_signal(py::module_& m);

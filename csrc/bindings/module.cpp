@@ -11,6 +11,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   def_batch(m);
   def_fp8(m);
   def_loss(m);
+  def_distill(m);
   def_optimizer(m);
   def_ema(m);
   def_signal(m);

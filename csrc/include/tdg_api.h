@@ -11,6 +11,7 @@
 
 #include "tdg_attn.h"
 #include "tdg_decode.h"
+#include "tdg_distill.h"
 
 extern "C" {
 
@@ -111,6 +112,11 @@ int tdg_xent(void* logits, int M, int V, int ldl, const void* labels, int lab64,
              hipStream_t st);
 int tdg_xent_stats(const float* row_loss, const float* row_correct, int M, const float* ntok,
                    float workers, float* step_out, float* accum, hipStream_t st);
+
+// ---------------------------------------------------------------- distill.hip
+// -1: T outside [1, 8], V outside [1, 65536] or alpha outside [0, 1]; -2: a
+// student or teacher row shorter than V, a null teacher; nothing launched
+int tdg_xent_distill(const tdg::DistillArgs* a, hipStream_t st);
 
 // ---------------------------------------------------------------- adam.hip
 // gstate: device state of the gradient-norm pass (clip factor, skip flag) or null

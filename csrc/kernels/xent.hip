@@ -13,15 +13,9 @@
 // logits buffer can feed the dgrad / wgrad GEMMs directly.
 #include "tdg_api.h"
 #include "tdg_common.h"
+#include "tdg_rowloss.h"
 
 namespace tdg {
-
-__device__ __forceinline__ void merge(float& m, float& s, float m2, float s2) {
-  const float mn = fmaxf(m, m2);
-  if (mn == -INFINITY) return;
-  s = s * __expf(m - mn) + s2 * __expf(m2 - mn);
-  m = mn;
-}
 
 template <typename LabT>
 __global__ __launch_bounds__(256) void xent_kernel(bf16_t* __restrict__ logits, int V, int ldl,
@@ -68,7 +62,7 @@ __global__ __launch_bounds__(256) void xent_kernel(bf16_t* __restrict__ logits, 
     sumx += __shfl_xor(sumx, o, 64);
     const float bv2 = __shfl_xor(bv, o, 64);
     const int bi2 = __shfl_xor(bi, o, 64);
-    if (bv2 > bv || (bv2 == bv && bi2 < bi)) { bv = bv2; bi = bi2; }
+    TDG_ARGMAX_TAKE(bv, bi, bv2, bi2)
   }
   if (lane == 0) { sm[w] = m; ss[w] = s; sv[w] = bv; si[w] = bi; }
   __shared__ float sx[4];
@@ -79,7 +73,7 @@ __global__ __launch_bounds__(256) void xent_kernel(bf16_t* __restrict__ logits, 
   for (int k = 1; k < 4; ++k) {
     merge(m, s, sm[k], ss[k]);
     sumx += sx[k];
-    if (sv[k] > bv || (sv[k] == bv && si[k] < bi)) { bv = sv[k]; bi = si[k]; }
+    TDG_ARGMAX_TAKE(bv, bi, sv[k], si[k])
   }
   const float lse = m + __logf(s);
   const bool valid = lab != 0;
@@ -160,7 +154,7 @@ __global__ __launch_bounds__(256) void xent_reg_kernel(bf16_t* __restrict__ logi
   for (int o = 32; o > 0; o >>= 1) {
     const float m2 = __shfl_xor(m, o, 64);
     const int i2 = __shfl_xor(bi, o, 64);
-    if (m2 > m || (m2 == m && i2 < bi)) { m = m2; bi = i2; }
+    TDG_ARGMAX_TAKE(m, bi, m2, i2)
     sumx += __shfl_xor(sumx, o, 64);
   }
   if (lane == 0) { r_m[w] = m; r_i[w] = bi; r_x[w] = sumx; }
@@ -168,7 +162,7 @@ __global__ __launch_bounds__(256) void xent_reg_kernel(bf16_t* __restrict__ logi
   m = r_m[0]; bi = r_i[0]; sumx = r_x[0];
 #pragma unroll
   for (int k = 1; k < 4; ++k) {
-    if (r_m[k] > m || (r_m[k] == m && r_i[k] < bi)) { m = r_m[k]; bi = r_i[k]; }
+    TDG_ARGMAX_TAKE(m, bi, r_m[k], r_i[k])
     sumx += r_x[k];
   }
   float se = 0.f;
@@ -204,7 +198,7 @@ __global__ __launch_bounds__(256) void xent_reg_kernel(bf16_t* __restrict__ logi
       float gv = 0.f;
       if (c < V && valid)
         gv = (__expf(bf2f((bf16_t)raw[k][e]) - lse) - off - (c == lab ? 1.f - smoothing : 0.f)) * scale;
-      g[e] = (short)f2bf(gv);
+      g[e] = pack_bf(gv);
     }
     wt.st16(x + c0, g);  // write-through: 115 MB of dlogits at Transformer-base
   }

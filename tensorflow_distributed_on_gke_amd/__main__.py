@@ -13,7 +13,9 @@ Kubernetes pod (THIS_POD_NAME set) it discovers the StatefulSet peers, runs
 the heartbeat barrier and launches one training process per local GPU
 (`--nproc`, default: all visible GPUs); locally it launches `--nproc`
 processes on 127.0.0.1, or runs in-process when started by
-torch.distributed.run (RANK set) or with one process.
+torch.distributed.run (RANK set) or with one process. With `--set
+distill_teacher=PREFIX[,PREFIX...]` the model is a student trained on the
+next-token distributions of those frozen models (train/distill.py).
 `test` is the reference's test.py + Tester (greedy translation, or beam
 search with --beam N --length-penalty ALPHA, or --sample N translations drawn
 per sentence); with --input / --output it translates a file, one sentence per

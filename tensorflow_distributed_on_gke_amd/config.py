@@ -136,6 +136,19 @@ class Settings:
     batch_tokens: int = 0
     length_bucket: int = 8
     corpus_on_device: bool = True
+    # extension, off without distill_teacher: word-level knowledge distillation
+    # (train/distill.py). distill_teacher: comma-separated weight prefixes (or
+    # snapshot directories, as warm_start) of 1 to 8 frozen teachers with the
+    # student's vocabularies; distill_weights: one positive number per teacher
+    # (default uniform); distill_alpha in (0, 1]: the teachers' share of the
+    # target, 0.5 when a teacher is given and it is left unset;
+    # distill_preset: the teachers' model preset (default: the student's
+    # configuration). Not with dtype=fp8. Validation stays the label cross
+    # entropy without a teacher
+    distill_teacher: Optional[str] = None
+    distill_weights: Optional[str] = None
+    distill_alpha: Optional[float] = None
+    distill_preset: Optional[str] = None
 
     def global_batch(self, world: int) -> int:
         return self.local_batch_size * world
@@ -182,6 +195,7 @@ def load_settings(path: Optional[str] = None, overrides: Optional[List[str]] = N
         raise ValueError(f"ema_decay must lie in [0, 1) (0: off), got {s.ema_decay!r}")
     check_accum_steps(s.accum_steps, s.dtype)
     check_batch_tokens(s.batch_tokens, s.data, s.length_bucket)
+    check_distill(s.distill_teacher, s.distill_weights, s.distill_alpha, s.dtype)
     return s
 
 
@@ -211,3 +225,47 @@ def check_batch_tokens(n: Any, data: str = "text", length_bucket: Any = 8) -> in
         raise ValueError(f"batch_tokens={n} needs data=text (token-budget batches are cut from a "
                          f"text corpus), got data={data!r}")
     return n
+
+
+DISTILL_TEACHERS_MAX = 8
+DISTILL_ALPHA_DEFAULT = 0.5
+
+
+def check_distill(teacher: Any, weights: Any = None, alpha: Any = None, dtype: str = "bf16"):
+    """The distillation settings as (prefixes, weights or None, alpha): ([],
+    None, 0.0) when off. distill_teacher names 1 to 8 comma-separated weight
+    prefixes; distill_weights one finite positive number per teacher;
+    distill_alpha lies in (0, 1] (default 0.5 with a teacher); weights or
+    alpha without a teacher, and a teacher with dtype=fp8, are refused.
+    ValueError otherwise."""
+    prefixes = [p.strip() for p in str(teacher).split(",") if p.strip()] if teacher else []
+    if isinstance(weights, (int, float)) and not isinstance(weights, bool):
+        weights = str(weights)  # (a single number given as a setting)
+    if not prefixes:
+        if teacher:
+            raise ValueError(f"distill_teacher names no weights prefix: {teacher!r}")
+        if weights:
+            raise ValueError(f"distill_weights={weights!r} without distill_teacher")
+        if alpha is not None:
+            raise ValueError(f"distill_alpha={alpha!r} without distill_teacher")
+        return [], None, 0.0
+    if len(prefixes) > DISTILL_TEACHERS_MAX:
+        raise ValueError(f"distill_teacher: at most {DISTILL_TEACHERS_MAX} teachers, got {len(prefixes)}")
+    if dtype == "fp8":
+        raise ValueError("distill_teacher with dtype=fp8 is not supported: the distillation step "
+                         "trains in bf16 (use dtype=bf16)")
+    w = None
+    if weights:
+        try:
+            w = [float(x) for x in str(weights).split(",") if x.strip()]
+        except ValueError:
+            raise ValueError(f"distill_weights must be comma-separated numbers, got {weights!r}") from None
+        if len(w) != len(prefixes):
+            raise ValueError(f"distill_weights has {len(w)} values for {len(prefixes)} teachers")
+        if not all(0.0 < x < float("inf") for x in w):
+            raise ValueError(f"distill_weights must be finite and > 0, got {weights!r}")
+    if alpha is None:
+        alpha = DISTILL_ALPHA_DEFAULT
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 < float(alpha) <= 1.0:
+        raise ValueError(f"distill_alpha must lie in (0, 1], got {alpha!r}")
+    return prefixes, w, float(alpha)

@@ -299,7 +299,9 @@ class Transformer:
                           accum: Optional[torch.Tensor] = None, backward: bool = True,
                           step_out: Optional[torch.Tensor] = None,
                           bump_ctr: bool = False, ntok_sum=None,
-                          ntok_total: Optional[torch.Tensor] = None) -> torch.Tensor:
+                          ntok_total: Optional[torch.Tensor] = None, teacher=None,
+                          alpha: float = 0.0,
+                          label_accum: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Teacher-forced forward, masked CE / accuracy, and (if `backward`)
         the full backward into the flat gradient buffer. Returns a device
         tensor [local_loss, accuracy] (loss already / workers, as the
@@ -312,9 +314,23 @@ class Transformer:
         normalised by instead of this batch's own (gradient accumulation under
         the global token mean: the count of the whole update, known before
         its first micro-batch -- ops.kernels.count_labels_multi); it is only
-        read. Pass workers = 1 with it and no ntok_sum."""
+        read. Pass workers = 1 with it and no ntok_sum.
+        teacher, alpha: word-level distillation (train/distill.py Teacher).
+        With a teacher and alpha > 0 the objective is the cross entropy
+        against (1 - alpha) * the smoothed labels + alpha * the teacher's
+        next-token distribution (ops.kernels.xent_distill); the returned loss
+        and `accum` then hold that objective, and label_accum (4 slots, as
+        accum) collects the label cross entropy alone. The teacher's forward
+        runs before the student's: the named workspaces are scratch of one
+        stream, and nothing may run between the student's forward and
+        backward. Without a teacher or with alpha = 0 this is the plain step."""
         if ntok_total is not None and ntok_sum is not None:
             raise ValueError("loss_and_backward: ntok_total and ntok_sum exclude each other")
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f"loss_and_backward: alpha must lie in [0, 1], got {alpha!r}")
+        distill = teacher is not None and alpha > 0.0
+        if distill and rt.fp8 is not None:
+            raise ValueError("loss_and_backward: distillation is not supported with dtype=fp8")
         cfg = self.cfg
         dev = src.device
         if dev.type == "cuda":  # split / lengths / token count / ctr: one launch
@@ -333,6 +349,7 @@ class Transformer:
             lengths = None
         B, T = tgt_in.shape
         M = B * T
+        t_logits = teacher.logits(src, tgt_in, lengths) if distill else None
         if step_out is None:
             step_out = torch.zeros(2, dtype=torch.float32, device=dev)
         grad_ctx = torch.enable_grad() if backward else torch.no_grad()
@@ -345,8 +362,16 @@ class Transformer:
             row_cor = K.workspace("row_correct", M, dev)[:M]
             if ntok_work is not None:
                 ntok_work.wait()
-            K.xent(logits, cfg.tgt_vocab, labels, ntok, workers, cfg.label_smoothing, row_loss,
-                   row_cor, write_grad=backward)
+            if distill:
+                row_lab = K.workspace("row_label", M, dev)[:M]
+                K.xent_distill(logits, t_logits, cfg.tgt_vocab, labels, ntok, workers,
+                               cfg.label_smoothing, alpha, teacher.weights, row_loss, row_cor,
+                               row_lab, write_grad=backward)
+                if label_accum is not None:
+                    K.xent_stats(row_lab, row_cor, ntok, workers, None, label_accum)
+            else:
+                K.xent(logits, cfg.tgt_vocab, labels, ntok, workers, cfg.label_smoothing, row_loss,
+                       row_cor, write_grad=backward)
             K.xent_stats(row_loss, row_cor, ntok, workers, step_out, accum)
             if not backward:
                 return step_out
@@ -369,16 +394,25 @@ class Transformer:
             nll = -logp.gather(1, lab.view(-1, 1)).squeeze(1)
             smooth = -logp.mean(dim=-1)
             row_loss = ((1 - eps) * nll + eps * smooth) * mask
+            if distill:
+                label_loss = row_loss.sum() / ntok / workers
+                target = K.distill_target(t_logits, cfg.tgt_vocab, lab, eps, alpha, teacher.weights)
+                row_loss = -(target * logp).sum(dim=-1) * mask
             correct = ((lg.argmax(dim=-1) == lab).to(torch.float32) * mask).sum()
             loss = row_loss.sum() / ntok / workers
             acc = correct / ntok
+            if distill and label_accum is not None:
+                label_accum += torch.stack([label_loss, acc, torch.tensor(1.0), ntok])
             step_out.copy_(torch.stack([loss, acc]).detach())
             if accum is not None:
                 accum += torch.stack([loss.detach(), acc.detach(), torch.tensor(1.0), ntok])
             if not backward:
                 return step_out
-            onehot = torch.nn.functional.one_hot(lab, cfg.tgt_vocab).to(torch.float32)
-            dl = (torch.softmax(lg, -1) - (1 - eps) * onehot - eps / cfg.tgt_vocab)
+            if distill:
+                dl = torch.softmax(lg, -1) - target
+            else:
+                onehot = torch.nn.functional.one_hot(lab, cfg.tgt_vocab).to(torch.float32)
+                dl = (torch.softmax(lg, -1) - (1 - eps) * onehot - eps / cfg.tgt_vocab)
             dl = dl * (mask / (ntok * workers)).view(-1, 1)
             fw, fb = self.final.w, self.final.b
             g_w = dl.t() @ dec2

@@ -27,7 +27,11 @@ accumulation: an optimizer update takes N consecutive batches of the epoch
 updates; with `batch_tokens` > 0 (data=text) length-sorted token-budget batches
 of varying row count (data/text.py), gathered on the device from a resident
 corpus (data/corpus.py) unless `corpus_on_device` is off, and `fill` and
-`real_tokens_per_s` (non-PAD positions) in the epoch line and record.
+`real_tokens_per_s` (non-PAD positions) in the epoch line and record; with
+`distill_teacher` word-level distillation from frozen teachers
+(train/distill.py), loaded on every rank after the student: the loss fields
+then hold the mixed objective, `label_loss` in the log lines and records the
+label cross entropy alone, and validation stays the plain one.
 
 Metric reads are the only host syncs: the device accumulators are summed over
 ranks (one small all-reduce) at log points, not every step.
@@ -45,7 +49,8 @@ import torch.distributed as dist
 
 from tensorflow_distributed_on_gke_amd.checkpoint import bundle
 from tensorflow_distributed_on_gke_amd.checkpoint.uploader import ModelUploader, make_storage
-from tensorflow_distributed_on_gke_amd.config import Settings, check_accum_steps, check_batch_tokens
+from tensorflow_distributed_on_gke_amd.config import (Settings, check_accum_steps, check_batch_tokens,
+                                                      check_distill)
 from tensorflow_distributed_on_gke_amd.data.synthetic import SyntheticPairs
 from tensorflow_distributed_on_gke_amd.models.layers import RunCtx
 from tensorflow_distributed_on_gke_amd.models.transformer import Transformer, model_config
@@ -60,9 +65,12 @@ RESUME_DIR = "resume"
 RESUME_PREFIX = "model_weights"
 
 
-def build_model(s: Settings, device) -> Transformer:
-    over = {k: getattr(s, k) for k in ("layers", "d_model", "heads", "d_ff") if getattr(s, k) is not None}
-    cfg = model_config(s.preset, src_vocab=s.src_vocab, tgt_vocab=s.tgt_vocab, dropout=s.dropout,
+def build_model(s: Settings, device, preset: Optional[str] = None) -> Transformer:
+    """The model of the settings; with `preset` a model of that preset alone
+    (a distillation teacher: the size overrides are the student's)."""
+    over = {k: getattr(s, k) for k in ("layers", "d_model", "heads", "d_ff")
+            if getattr(s, k) is not None and preset is None}
+    cfg = model_config(preset or s.preset, src_vocab=s.src_vocab, tgt_vocab=s.tgt_vocab, dropout=s.dropout,
                        label_smoothing=s.label_smoothing,
                        max_src_len=max(s.max_len, s.src_len), max_tgt_len=max(s.max_len, s.tgt_len + 1),
                        **over)
@@ -91,6 +99,8 @@ class Trainer:
         s, info = self.settings, self.info
         check_accum_steps(s.accum_steps, s.dtype)
         check_batch_tokens(s.batch_tokens, s.data, s.length_bucket)
+        t_prefixes, t_weights, t_alpha = check_distill(s.distill_teacher, s.distill_weights,
+                                                       s.distill_alpha, s.dtype)
         if s.worker_count != info.world and info.chief:
             # the reference used worker_count both as expected size and loss
             # divisor; the runtime world size wins
@@ -120,8 +130,20 @@ class Trainer:
         if s.dtype == "fp8" and info.device.type == "cuda":
             from tensorflow_distributed_on_gke_amd.ops.fp8 import Fp8State
             self.fp8 = Fp8State(self.model)
+        # distillation: frozen teachers, built after the student and loaded on
+        # every rank (they are not part of the broadcast training state)
+        self.teacher = None
+        if t_prefixes:
+            from tensorflow_distributed_on_gke_amd.train.distill import load_teacher
+            self.teacher = load_teacher(
+                t_prefixes, lambda: build_model(s, info.device, s.distill_preset), t_weights)
+            if info.chief:
+                self.log(f"distillation: {len(t_prefixes)} teacher(s) "
+                         f"({s.distill_preset or 'the student configuration'}), weights "
+                         f"{[round(w, 4) for w in self.teacher.weights]}, alpha {t_alpha}")
         self.step_fn = TrainStep(self.model, self.opt, self.ddp, workers=info.world, seed=s.seed + 17,
-                                 fp8_state=self.fp8, loss_mode=s.loss_mode, accum_steps=s.accum_steps)
+                                 fp8_state=self.fp8, loss_mode=s.loss_mode, accum_steps=s.accum_steps,
+                                 teacher=self.teacher, distill_alpha=t_alpha)
         # every micro-batch of every rank is one replica of the update
         self._replicas = info.world * s.accum_steps
         # summed accuracy over replicas: a mean of per-replica ratios, or (global
@@ -247,6 +269,15 @@ class Trainer:
         return {"grad_norm": self.opt.last_grad_norm(), "grad_norm_max": c["grad_norm_max"],
                 "clipped_steps": c["clipped_steps"], "skipped_steps": c["skipped_steps"]}
 
+    def _label_record(self, n: float) -> Dict[str, float]:
+        """Distillation: {"label_loss": the label cross entropy of the epoch so
+        far} next to the objective the loss fields hold; {} without a teacher.
+        n: the updates the accumulators hold."""
+        la = self.step_fn.label_accum
+        if la is None:
+            return {}
+        return {"label_loss": float(self._reduce(la)[0]) / n}
+
     def _to_dev(self, batch):
         dev = self.info.device
         return batch[0].to(dev, non_blocking=True), batch[1].to(dev, non_blocking=True)
@@ -338,6 +369,8 @@ class Trainer:
         for epoch in range(self.start_epoch, s.epochs):
             t0 = time.time()
             self.step_fn.accum.zero_()
+            if self.step_fn.label_accum is not None:
+                self.step_fn.label_accum.zero_()
             epoch_tokens = 0
             real_tokens = 0  # token-budget batches: non-PAD positions, from the plan's lengths
             if N > 1:  # the epoch's own first batch (the previous one's tail is skipped)
@@ -390,9 +423,11 @@ class Trainer:
                     a = self._reduce(self.step_fn.accum)
                     n = max(float(a[2]) / self._replicas, 1.0)
                     st = summarize(self.timer.drain())
+                    lab_rec = self._label_record(n)
                     if info.chief:
                         self.log(f"Epoch {epoch + 1} Batch {batch} Loss {float(a[0]) / n:.4f} "
-                                 f"Accuracy {float(a[1]) / (n * self._acc_div):.4f}")
+                                 f"Accuracy {float(a[1]) / (n * self._acc_div):.4f}"
+                                 + (f" label_loss {lab_rec['label_loss']:.4f}" if lab_rec else ""))
                         if self.step_fn.bucketed and self.step_fn.captured:
                             gs = self.step_fn.graph_stats
                             self.log(f"graph cache: {self.step_fn.cached_shapes} batch shapes captured "
@@ -400,9 +435,10 @@ class Trainer:
                                      f"replays {gs['replays']})")
                         self.metrics.write(kind="train", epoch=epoch + 1, batch=batch, step=self.global_step,
                                            loss=float(a[0]) / n, accuracy=float(a[1]) / (n * self._acc_div),
-                                           **st, **self._clip_record())
+                                           **st, **lab_rec, **self._clip_record())
             a = self._reduce(self.step_fn.accum)
             n = max(float(a[2]) / self._replicas, 1.0)
+            lab_rec = self._label_record(n)
             train_loss = float(a[0]) / n
             train_acc = float(a[1]) / (n * self._acc_div)
             if info.device.type == "cuda":
@@ -427,10 +463,12 @@ class Trainer:
                 tok_rec = {"real_tokens_per_s": real_tokens / max(train_time, 1e-9),
                            "fill": real_tokens / max(epoch_tokens, 1)}
                 self.token_history.append(tok_rec)
-            self.metrics.write(kind="epoch", **st.__dict__, **ema_rec, **tok_rec, **self._clip_record())
+            self.metrics.write(kind="epoch", **st.__dict__, **ema_rec, **tok_rec, **lab_rec,
+                               **self._clip_record())
             if info.chief:
                 self.log(f"Epoch {epoch + 1} Loss {train_loss:.4f} Accuracy {train_acc:.4f} "
-                         f"Test Loss {val['loss']:.4f} Test Accuracy {val['acc']:.4f}")
+                         f"Test Loss {val['loss']:.4f} Test Accuracy {val['acc']:.4f}"
+                         + (f" label_loss {lab_rec['label_loss']:.4f}" if lab_rec else ""))
                 if ema_val is not None:
                     self.log(f"EMA Test Loss {ema_val['loss']:.4f} Test Accuracy {ema_val['acc']:.4f}")
                 if tok_rec:

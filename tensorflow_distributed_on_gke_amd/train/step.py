@@ -80,8 +80,22 @@ class TrainStep:
     def __init__(self, model: Transformer, opt: Adam, ddp: Optional[DataParallel], workers: float,
                  seed: int = 0, dropout: Optional[float] = None, fp8_state=None,
                  defer_wgrad: Optional[bool] = None, loss_mode: str = "replica_mean",
-                 accum_steps: int = 1):
+                 accum_steps: int = 1, teacher=None, distill_alpha: float = 0.0):
+        """teacher, distill_alpha: word-level distillation (train/distill.py).
+        With a Teacher and distill_alpha in (0, 1] every micro-batch runs the
+        teacher's forward before the student's -- inside the captured step,
+        whichever way it is captured -- and trains on the mixed target; `accum`
+        and `last` then hold that objective and `label_accum` the label
+        cross entropy alone."""
         self.accum_steps = check_accum_steps(accum_steps, "fp8" if fp8_state is not None else "bf16")
+        if not 0.0 <= float(distill_alpha) <= 1.0:
+            raise ValueError(f"distill_alpha must lie in [0, 1], got {distill_alpha!r}")
+        self.teacher = teacher if teacher is not None and distill_alpha > 0.0 else None
+        self.distill_alpha = float(distill_alpha) if self.teacher is not None else 0.0
+        if self.teacher is not None:
+            if fp8_state is not None:
+                raise ValueError("distillation with dtype=fp8 is not supported (use dtype=bf16)")
+            self.teacher.check_student(model)
         self.model = model
         self.opt = opt
         self.ddp = ddp
@@ -148,6 +162,9 @@ class TrainStep:
         # metric accumulators [sum loss, sum acc, n steps, n tokens] (device)
         self.accum = torch.zeros(4, dtype=torch.float32, device=dev)
         self.last = torch.zeros(2, dtype=torch.float32, device=dev)
+        # distillation: the label cross entropy alone, same four slots as accum
+        self.label_accum = (torch.zeros(4, dtype=torch.float32, device=dev)
+                            if self.teacher is not None else None)
         self.graph = None
         self.segments: Optional[SegmentedGraph] = None
         self._static: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
@@ -198,6 +215,8 @@ class TrainStep:
             ts += [self.opt.norm_state, self.opt.norm_counters]
         if self.opt.ema is not None:
             ts += [self.opt.ema.avg, self.opt.ema.count]
+        if self.label_accum is not None:
+            ts += [self.label_accum]  # (the teacher's weights never change: not state)
         if self.accum_steps > 1:
             # a capture between two micro-batches warms up on the partial sums
             ts += [self.model.store.flat_grad]
@@ -237,7 +256,8 @@ class TrainStep:
         try:
             self.model.loss_and_backward(src, tgt, self.rt, self.workers, accum=self.accum,
                                          step_out=self.last, bump_ctr=True, ntok_sum=self._ntok_sum,
-                                         ntok_total=self._ntok_total)
+                                         ntok_total=self._ntok_total, teacher=self.teacher,
+                                         alpha=self.distill_alpha, label_accum=self.label_accum)
         finally:
             self.rt.accumulate = False
             self.last_micro = True
