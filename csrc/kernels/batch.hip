@@ -12,8 +12,8 @@
 // [0, n_rows), or offsets that are negative, decreasing or past the end of
 // the token buffer, give an all-PAD row; a row longer than L is cut at L.
 // Each such (row, side) bumps the optional `bad` counter word, which the
-// host reads at log points (ops/kernels.py check_gather_rows): a wrong batch
-// plan is an error message, never an out-of-bounds access.
+// host reads at log points (ops/kernels/batch.py check_gather_rows): a wrong
+// batch plan is an error message, never an out-of-bounds access.
 //
 // The launch moves on the order of 100 KB and is launch-bound, so it is kept
 // plain: one 64-lane wave per output row, lanes along the row (coalesced

@@ -14,7 +14,7 @@
 namespace tdg {
 
 // word of the gradient-norm device state that holds the skip flag (adam.hip
-// GNS_SKIP, ops/kernels.py NORM_SKIP)
+// GNS_SKIP, ops/kernels/optimizer.py NORM_SKIP)
 constexpr int EMA_GNS_SKIP = 3;
 
 __device__ __forceinline__ void ema4(float4& ee, const float4& pp, float omd) {

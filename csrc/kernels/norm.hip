@@ -250,8 +250,8 @@ void ln_bwd_d(const void* dy, const void* hsave, const float* mean, const float*
               int accumulate, int skip_reduce, int rpb, void* ds8, const float* s8, unsigned* amax8,
               const void* kbits, hipStream_t st) {
   const uint32_t thresh = dropout_thresh(p);
-  // rpb rows per block (kernels.py ln_bwd_nparts): 16 on 4 waves, 32 / 64 on
-  // 8 waves (fewer partial rows for the fold); RPW rows per wave per pass
+  // rpb rows per block (ops/kernels/layernorm.py ln_bwd_nparts): 16 on 4 waves,
+  // 32 / 64 on 8 waves (fewer partial rows for the fold); RPW rows per wave per pass
   constexpr int RPW = D >= 1024 ? 2 : 4;
   const int nb = cdiv(M, rpb);
   float* pg = ws;

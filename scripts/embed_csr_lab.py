@@ -9,6 +9,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from tensorflow_distributed_on_gke_amd.ops import kernels as kk  # noqa: E402
+from tensorflow_distributed_on_gke_amd.ops.kernels import embedding  # noqa: E402
 
 dev = "cuda"
 for M, V, D, pad in [(1024, 1000, 512, 0.0), (8192, 1000, 512, 0.0), (8192, 7765, 512, 0.0),
@@ -21,7 +22,7 @@ for M, V, D, pad in [(1024, 1000, 512, 0.0), (8192, 1000, 512, 0.0), (8192, 7765
     ctr = torch.zeros(1, dtype=torch.int64, device=dev)
     dt = torch.zeros(V, D, device=dev)
     for csr in (True, False):
-        kk.EMBED_CSR = csr
+        embedding.EMBED_CSR = csr
         for _ in range(20):
             kk.embed_bwd(tok, dout, dt, math.sqrt(D), 0.1, 1, ctr, 3)
         torch.cuda.synchronize()

@@ -2,7 +2,7 @@
 """In-situ GEMM tile selection: time whole eager training steps while one
 GEMM shape's tile config is varied, all others held at the current table.
 
-The isolated autotuner (ops/kernels.py) times a GEMM back-to-back with warm
+The isolated autotuner (ops/tuning.py) times a GEMM back-to-back with warm
 caches; inside the step, epilogue operands (the ReLU mask written in forward,
 the residual gradient) and weights are cold and neighbouring kernels contend
 for L2/MALL, so the best isolated tile is not always the best in the step.
@@ -12,6 +12,7 @@ winning table is written as JSON (same format as gemm_tuned_gfx950.json).
     python scripts/tune_in_model.py --preset base --out gpurun_out/tuned_inmodel.json
 """
 import argparse
+import importlib
 import json
 import os
 import sys
@@ -24,6 +25,10 @@ from tensorflow_distributed_on_gke_amd.models.transformer import Transformer, mo
 from tensorflow_distributed_on_gke_amd.ops import kernels as kk  # noqa: E402
 from tensorflow_distributed_on_gke_amd.train.optim import Adam  # noqa: E402
 from tensorflow_distributed_on_gke_amd.train.step import TrainStep  # noqa: E402
+
+# the module that owns the tuned table (`kk.gemm` is the function of that name); linear_fwd and
+# its siblings call its `gemm`, so the spy goes there too
+kgemm = importlib.import_module("tensorflow_distributed_on_gke_amd.ops.kernels.gemm")
 
 CANDS = [(c, 1) for c in (0, 4, 5, 6, 9, 10, 12, 13, 14, 20, 21, 22)]
 
@@ -57,22 +62,22 @@ def main():
 
     # record the GEMM keys one step uses (and whether the library path applies)
     seen = {}
-    orig = kk.gemm
+    orig = kgemm.gemm
 
     def spy(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc, b_kc, epi=kk.EPI_NONE, bias=None, aux=None,
             ldaux=0, alpha=1.0, beta=0.0, cfg=None):
-        Mk, Kk = (M, kk._tok_bucket(K)) if (not a_kc and not b_kc) else (kk._tok_bucket(M), K)
+        Mk, Kk = (M, kgemm._tok_bucket(K)) if (not a_kc and not b_kc) else (kgemm._tok_bucket(M), K)
         key = (Mk, N, Kk, a_kc, b_kc, epi, Cout.dtype, ldc % 8 == 0, beta != 0.0)
         if cfg is None and (not args.epi or epi in args.epi):
             seen.setdefault(key, [0, False])[0] += 1
         return orig(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc, b_kc, epi, bias, aux, ldaux, alpha, beta,
                     cfg)
 
-    kk.gemm = spy
+    kgemm.gemm = spy
     for _ in range(3):
         step(s, t)
     torch.cuda.synchronize()
-    kk.gemm = orig
+    kgemm.gemm = orig
 
     def timed():
         if args.graph:
@@ -93,22 +98,22 @@ def main():
         M, N, K = key[:3]
         if 2.0 * M * N * K * calls < args.min_flops:
             continue
-        cur = kk._TUNED.get(key, (None,))[0]
+        cur = kgemm._TUNED.get(key, (None,))[0]
         cands = list(args.cands or CANDS)
         if cur is not None and cur not in cands:
             cands.append(cur)
         times = {c: [] for c in cands}
         for _ in range(args.rounds):
             for c in cands:
-                kk._TUNED[key] = (c, c)
+                kgemm._TUNED[key] = (c, c)
                 try:
                     times[c].append(timed())
                 except RuntimeError:
                     times[c].append(float("inf"))
         med = {c: sorted(v)[len(v) // 2] for c, v in times.items()}
         best = min(med, key=med.get)
-        kk._TUNED[key] = (best, best)
-        print(json.dumps({"key": kk._key_str(key), "calls": calls, "was": cur, "best": best,
+        kgemm._TUNED[key] = (best, best)
+        print(json.dumps({"key": kgemm._key_str(key), "calls": calls, "was": cur, "best": best,
                           "us_step": {f"{c[0]}": round(v, 1) for c, v in med.items()}}), flush=True)
     final = timed()
     print(f"end: {final:.1f} us/step (start {base:.1f})", flush=True)

@@ -15,10 +15,10 @@ from typing import Optional
 
 import torch
 
-from tensorflow_distributed_on_gke_amd.models.layers import (LN_EPS, CrossKVFn, KVGrad, RunCtx,
-                                                             _ref_attn_fwd)
+from tensorflow_distributed_on_gke_amd.models.layers import LN_EPS, CrossKVFn, KVGrad, RunCtx
 from tensorflow_distributed_on_gke_amd.models.transformer import Transformer
 from tensorflow_distributed_on_gke_amd.ops import kernels as K
+from tensorflow_distributed_on_gke_amd.ops.kernels.attention import _ref_attn_fwd
 
 
 # --------------------------------------------------------------- single-token ops (GPU kernels / CPU f32)

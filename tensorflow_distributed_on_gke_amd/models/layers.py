@@ -45,6 +45,7 @@ from tensorflow_distributed_on_gke_amd.models.wgrad import (  # noqa: F401 (Wgra
     WgradQueue, _beta, _fold_bias_later, _fp8_grad_bias, _ready, _wgrad)
 from tensorflow_distributed_on_gke_amd.ops import kernels as K
 from tensorflow_distributed_on_gke_amd.ops import fp8, philox
+from tensorflow_distributed_on_gke_amd.ops.kernels.attention import _ref_attn_fwd
 
 LN_EPS = 1e-6
 
@@ -284,23 +285,7 @@ class EmbedFn(torch.autograd.Function):
 
 
 # =============================================================================== attention (CPU reference core)
-def _ref_attn_fwd(q, k, v, kv_len, causal, scale):
-    """q [B,Lq,H,hd] ... -> out [B,Lq,H,hd], probs [B,H,Lq,Lk]. Masked logits
-    get -1e9 added exactly as the reference does (transformer_model.py:101-102)."""
-    s = torch.einsum("bqhd,bkhd->bhqk", q, k) * scale
-    B, H, Lq, Lk = s.shape
-    mask = torch.zeros(B, 1, Lq, Lk, dtype=s.dtype, device=s.device)
-    keys = torch.arange(Lk, device=s.device)
-    if kv_len is not None:
-        mask = mask + (keys.view(1, 1, 1, Lk) >= kv_len.view(B, 1, 1, 1).to(keys.device)).to(s.dtype)
-    if causal:
-        qs = torch.arange(Lq, device=s.device)
-        mask = torch.maximum(mask, (keys.view(1, Lk) > qs.view(Lq, 1)).to(s.dtype).view(1, 1, Lq, Lk))
-    p = torch.softmax(s + mask * -1e9, dim=-1)
-    out = torch.einsum("bhqk,bkhd->bqhd", p, v)
-    return out, p
-
-
+# (the forward, _ref_attn_fwd, lives next to the kernel it stands in for: ops/kernels/attention.py)
 def _ref_attn_bwd(q, k, v, p, dout, scale):
     dv = torch.einsum("bhqk,bqhd->bkhd", p, dout)
     dp = torch.einsum("bqhd,bkhd->bhqk", dout, v)

@@ -5,8 +5,9 @@ I/O, CRC32C, data loader). Both are built in-tree by `_build.py`.
 
 GPU ops never fall back to PyTorch: if `_C` is missing or was built for another
 architecture, the first GPU op raises. CPU tensors take the plain-PyTorch
-reference paths inside the layer ops (`models/layers.py`, e.g.
-`_ref_attn_fwd`), used by the CPU test-suite and the tiny CPU config.
+reference paths inside the layer ops (`models/layers.py`; the attention
+forward, `_ref_attn_fwd`, in `ops/kernels/attention.py`), used by the CPU
+test-suite and the tiny CPU config.
 """
 from __future__ import annotations
 

@@ -27,8 +27,9 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
+from tensorflow_distributed_on_gke_amd.ops import tuning
 from tensorflow_distributed_on_gke_amd.ops._ext import C
-from tensorflow_distributed_on_gke_amd.ops import kernels as K
+from tensorflow_distributed_on_gke_amd.ops.kernels.workspace import NUM_CU, workspace
 
 FP8 = torch.float8_e4m3fn
 BF8 = torch.float8_e5m2  # gradient format of the fp8 backward
@@ -189,7 +190,7 @@ def quantize_colsum(x: torch.Tensor, meta: Fp8Meta, i: int, key: str):
     M, N = x.shape
     nparts = math.ceil(M / 256)
     x8 = torch.empty(M, N, dtype=meta.dtype, device=x.device)
-    part = K.workspace("qcs_" + key, nparts * N, x.device)[: nparts * N]
+    part = workspace("qcs_" + key, nparts * N, x.device)[: nparts * N]
     C().fp8_quant_colsum(x, x8, meta.s(i), meta.a(i), part, meta.fmt)
     return x8, part, nparts
 
@@ -228,8 +229,8 @@ def gemm_fp8(a8, b8, bias, meta: Fp8Meta, ia: int, ib: int, relu: bool = False,
         key = (M, N, Kd, epi, y8 is not None, want_y)
         cfg = _TUNED.get(key)
         if cfg is None:
-            if K.AUTOTUNE and a8.is_cuda and not torch.cuda.is_current_stream_capturing():
-                cfg = _autotune(run)
+            if tuning.AUTOTUNE and a8.is_cuda and not torch.cuda.is_current_stream_capturing():
+                cfg = tuning.time_candidates(_CANDS, run, 5)
             else:
                 cfg = choose_fp8(M, N, Kd)
             _TUNED[key] = cfg
@@ -269,7 +270,7 @@ def gemm_bf8_dgrad(g8, gmeta: Fp8Meta, ig: int, w8, wmeta: Fp8Meta, iw: int,
         # (deferred: the partials must survive until the fold -- a workspace
         # per output)
         key = "fp8_colsum" if defer is None else f"fp8_colsum_{colsum_out.data_ptr()}"
-        ws = K.workspace(key, nparts * N, g8.device)
+        ws = workspace(key, nparts * N, g8.device)
     epi = (EPI_DRELU if aux is not None else EPI_NONE) | (EPI_B_NCONTIG if w_plain else 0)
     if colsum_out is not None and defer is not None:
         epi |= EPI_CS_DEFER
@@ -328,7 +329,7 @@ def choose_fp8(M: int, N: int, Kd: int) -> int:
     128x128 on 4 waves whenever that fills the CUs -- it beat 256x128 / 8
     waves on every Transformer-big forward shape, 3-14 % (qkv 42.7 vs 47.0 us,
     xkv6 160.6 vs 186.6; profiles/r3/fp8_gemm_sweep.jsonl)."""
-    if -(-M // 128) * -(-N // 128) >= K.NUM_CU:
+    if -(-M // 128) * -(-N // 128) >= NUM_CU:
         return 0  # 128x128, 4 waves, 2 stages
     return 5
 
@@ -340,47 +341,23 @@ def _tkey_str(k: tuple) -> str:
 def save_tuned(path: str) -> None:
     """Persist the fp8 forward GEMM tile choices (JSON: "M,N,K,epi,y8,y" ->
     cfg), e.g. from scripts/tune_fp8_in_model.py."""
-    import json
+    tuning.save_table(path, ((_tkey_str(k), v) for k, v in sorted(_TUNED.items())))
 
-    with open(path, "w") as f:
-        json.dump({_tkey_str(k): v for k, v in sorted(_TUNED.items())}, f, indent=0)
+
+def _parse_tkey(ks: str) -> tuple:
+    M, N, Kd, epi, y8, y = (int(x) for x in ks.split(","))
+    return (M, N, Kd, epi, bool(y8), bool(y))
 
 
 def load_tuned(path: str) -> int:
-    import json
-
-    if not os.path.exists(path):
-        return 0
-    with open(path) as f:
-        data = json.load(f)
-    for ks, v in data.items():
-        M, N, Kd, epi, y8, y = (int(x) for x in ks.split(","))
-        _TUNED[(M, N, Kd, epi, bool(y8), bool(y))] = int(v)
-    return len(data)
+    table = tuning.load_table(path, _parse_tkey, int)
+    _TUNED.update(table)
+    return len(table)
 
 
 # in-model measured tiles of the Transformer-big fp8 forward GEMMs
 # (scripts/tune_fp8_in_model.py); shapes not in it: choose_fp8
-TUNED_FILE = os.environ.get("TDG_FP8_TUNED_FILE") or os.path.join(
-    os.path.dirname(os.path.abspath(__file__)), "fp8_tuned_gfx950.json")
-
-
-def _autotune(run) -> int:
-    times = {}
-    for rnd in range(2):
-        for c in _CANDS:
-            try:
-                run(c)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(5):
-                    run(c)
-                e1.record()
-                e1.synchronize()
-                times[c] = min(times.get(c, math.inf), e0.elapsed_time(e1))
-            except RuntimeError:
-                continue
-    return min(times, key=times.get)
+TUNED_FILE = tuning.table_file("TDG_FP8_TUNED_FILE", "fp8_tuned_gfx950.json")
 
 
 class Fp8Weights:

@@ -3,7 +3,7 @@ shared by the CPU and the GPU tests: the CPU file proves every case reachable
 and decided and the reference a correct sampler, the GPU file holds the kernel
 to it.
 
-The reference implements the definition (ops/kernels.py sample_token) in
+The reference implements the definition (ops/kernels/decode.py sample_token) in
 float64 with the exact uniforms of ops/philox.py. Two quantities say whether
 an f32 implementation must agree with it on a row:
 

@@ -38,11 +38,11 @@ def _batch(B, S, T1, V1, V2, seed, pad=(0, 0)):
 
 def _make(model="tiny", accum_steps=1, loss_mode="replica_mean", seed=3, **opt_kw):
     from tensorflow_distributed_on_gke_amd.models.transformer import Transformer, model_config
-    from tensorflow_distributed_on_gke_amd.ops import kernels as kk
+    from tensorflow_distributed_on_gke_amd.ops import tuning
     from tensorflow_distributed_on_gke_amd.train.optim import Adam
     from tensorflow_distributed_on_gke_amd.train.step import TrainStep
 
-    kk.AUTOTUNE = False  # identical GEMM configs in every run
+    tuning.AUTOTUNE = False  # identical GEMM configs in every run
     cfg = model_config("tiny", dropout=0.0, **MODELS[model])
     m = Transformer(cfg).build(DEV, seed=seed)
     opt = Adam(m.store, cfg.d_model, **{**ADAM, **opt_kw})
@@ -283,13 +283,13 @@ def _dp_worker(rank, world, port, out, loss_mode, graph, comm_thread):
     from tensorflow_distributed_on_gke_amd.train import step as step_mod
     step_mod.DP_OVERLAP_OPT = "tail"
     from tensorflow_distributed_on_gke_amd.models.transformer import Transformer, model_config
-    from tensorflow_distributed_on_gke_amd.ops import kernels as kk
+    from tensorflow_distributed_on_gke_amd.ops import tuning
     from tensorflow_distributed_on_gke_amd.parallel import dist as tdist
     from tensorflow_distributed_on_gke_amd.parallel.ddp import DataParallel
     from tensorflow_distributed_on_gke_amd.train.optim import Adam
     from tensorflow_distributed_on_gke_amd.train.step import TrainStep
 
-    kk.AUTOTUNE = False
+    tuning.AUTOTUNE = False
     N = 2
     info = tdist.init_distributed("cuda")
     m = Transformer(model_config("tiny", dropout=0.0, **DP_CFG)).build(info.device, seed=1 + rank)
@@ -363,13 +363,13 @@ def _select_worker(rank, port, out):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1",
                       LOCAL_RANK="0", TDG_DP_GRAPH="seg")
     from tensorflow_distributed_on_gke_amd.models.transformer import Transformer, model_config
-    from tensorflow_distributed_on_gke_amd.ops import kernels as kk
+    from tensorflow_distributed_on_gke_amd.ops import tuning
     from tensorflow_distributed_on_gke_amd.parallel import dist as tdist
     from tensorflow_distributed_on_gke_amd.parallel.ddp import DataParallel
     from tensorflow_distributed_on_gke_amd.train.optim import Adam
     from tensorflow_distributed_on_gke_amd.train.step import TrainStep
 
-    kk.AUTOTUNE = False
+    tuning.AUTOTUNE = False
     info = tdist.init_distributed("cuda", force=True)
     V = MODELS["tiny"]
     updates = [[_batch(4, 32, 33, V["src_vocab"], V["tgt_vocab"], seed=5 * u + k, pad=(1 + k, 2 + u))

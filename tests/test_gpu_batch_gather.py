@@ -194,11 +194,11 @@ def test_host_and_device_assembly_agree(corpus, world, rank):
 
 def _run_plan_batches(batches, bucketed):
     from tensorflow_distributed_on_gke_amd.models.transformer import Transformer, model_config
-    from tensorflow_distributed_on_gke_amd.ops import kernels as kk
+    from tensorflow_distributed_on_gke_amd.ops import tuning
     from tensorflow_distributed_on_gke_amd.train.optim import Adam
     from tensorflow_distributed_on_gke_amd.train.step import TrainStep
 
-    kk.AUTOTUNE = False  # identical GEMM configs in both runs
+    tuning.AUTOTUNE = False  # identical GEMM configs in both runs
     cfg = model_config("tiny", d_model=256, heads=4, d_ff=1024, src_vocab=500, tgt_vocab=400, dropout=0.1)
     m = Transformer(cfg).build(DEV, seed=4)
     opt = Adam(m.store, cfg.d_model, lr=0.003)

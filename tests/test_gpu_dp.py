@@ -54,8 +54,8 @@ def _worker(rank, world, port, out, opt_mode, loss_mode, graph, comm_thread="1",
     from tensorflow_distributed_on_gke_amd.train.optim import Adam
     from tensorflow_distributed_on_gke_amd.train.step import TrainStep
 
-    from tensorflow_distributed_on_gke_amd.ops import kernels as kk
-    kk.AUTOTUNE = False  # same GEMM configs as the reference process (bf16 rounding)
+    from tensorflow_distributed_on_gke_amd.ops import tuning
+    tuning.AUTOTUNE = False  # same GEMM configs as the reference process (bf16 rounding)
     info = tdist.init_distributed("cuda")
     m = Transformer(model_config("tiny", **CFG)).build(info.device, seed=1 + rank)
     opt = Adam(m.store, m.cfg.d_model, **ADAM)
@@ -110,7 +110,7 @@ def _worker(rank, world, port, out, opt_mode, loss_mode, graph, comm_thread="1",
 def test_gpu_dp_rehearsal_matches_single_process(tmp_path, world, opt_mode, loss_mode, graph, comm_thread,
                                                  comm_bf16, signal, monkeypatch):
     from tensorflow_distributed_on_gke_amd.models.layers import RunCtx
-    from tensorflow_distributed_on_gke_amd.ops import kernels as kk
+    from tensorflow_distributed_on_gke_amd.ops import tuning
     from tensorflow_distributed_on_gke_amd.models.transformer import Transformer, model_config
     from tensorflow_distributed_on_gke_amd.train.optim import Adam
 
@@ -127,7 +127,7 @@ def test_gpu_dp_rehearsal_matches_single_process(tmp_path, world, opt_mode, loss
     # Autotuning off on both sides: the ranks and this process would otherwise
     # time-pick GEMM tiles independently, and a different summation order
     # flips bf16 roundings of intermediate gradients (~1e-2 relative drift)
-    monkeypatch.setattr(kk, "AUTOTUNE", False)
+    monkeypatch.setattr(tuning, "AUTOTUNE", False)
     m = Transformer(model_config("tiny", **CFG)).build("cuda", seed=1)
     init = m.store.flat.clone()
     opt = Adam(m.store, m.cfg.d_model, **ADAM)
@@ -174,13 +174,13 @@ def _fp8_worker(rank, world, port, out, graph, comm_thread="force"):
     step_mod.DP_OVERLAP_OPT = "tail"
     from tensorflow_distributed_on_gke_amd.models.transformer import Transformer, model_config
     from tensorflow_distributed_on_gke_amd.ops import fp8 as F
-    from tensorflow_distributed_on_gke_amd.ops import kernels as kk
+    from tensorflow_distributed_on_gke_amd.ops import tuning
     from tensorflow_distributed_on_gke_amd.parallel import dist as tdist
     from tensorflow_distributed_on_gke_amd.parallel.ddp import DataParallel
     from tensorflow_distributed_on_gke_amd.train.optim import Adam
     from tensorflow_distributed_on_gke_amd.train.step import TrainStep
 
-    kk.AUTOTUNE = False
+    tuning.AUTOTUNE = False
     info = tdist.init_distributed("cuda")
     # hd 64 and sequences > 128: the e4m3 attention forward runs too
     cfg = model_config("tiny", d_model=128, heads=2, d_ff=512, src_vocab=1000, tgt_vocab=1000,

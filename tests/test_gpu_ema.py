@@ -177,11 +177,11 @@ def _batches(dev):
 
 def _make(fp8, **opt_kw):
     from tensorflow_distributed_on_gke_amd.models.transformer import Transformer, model_config
-    from tensorflow_distributed_on_gke_amd.ops import kernels as kk
+    from tensorflow_distributed_on_gke_amd.ops import tuning
     from tensorflow_distributed_on_gke_amd.train.optim import Adam
     from tensorflow_distributed_on_gke_amd.train.step import TrainStep
 
-    kk.AUTOTUNE = False  # identical GEMM configs in every run
+    tuning.AUTOTUNE = False  # identical GEMM configs in every run
     cfg = model_config("tiny", d_model=256, heads=4, d_ff=1024, src_vocab=500, tgt_vocab=400, dropout=0.1)
     m = Transformer(cfg).build(DEV, seed=3)
     opt = Adam(m.store, cfg.d_model, lr=0.003, **opt_kw)
@@ -321,13 +321,13 @@ def _worker(rank, world, port, out):
     step_mod.WAVE_TILES = 37  # small waves: problems cut across launches
     step_mod.DP_OVERLAP_OPT = "tail"
     from tensorflow_distributed_on_gke_amd.models.transformer import Transformer, model_config
-    from tensorflow_distributed_on_gke_amd.ops import kernels as kk
+    from tensorflow_distributed_on_gke_amd.ops import tuning
     from tensorflow_distributed_on_gke_amd.parallel import dist as tdist
     from tensorflow_distributed_on_gke_amd.parallel.ddp import DataParallel
     from tensorflow_distributed_on_gke_amd.train.optim import Adam
     from tensorflow_distributed_on_gke_amd.train.step import TrainStep
 
-    kk.AUTOTUNE = False
+    tuning.AUTOTUNE = False
     info = tdist.init_distributed("cuda")
     m = Transformer(model_config("tiny", **CFG)).build(info.device, seed=1 + rank)
     opt = Adam(m.store, m.cfg.d_model, lr=0.05, eps=1.0, ema_decay=0.9, ema_warmup=True)

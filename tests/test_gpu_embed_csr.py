@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from tensorflow_distributed_on_gke_amd.ops import kernels as kk
+from tensorflow_distributed_on_gke_amd.ops.kernels import embedding
 from tensorflow_distributed_on_gke_amd.ops import philox
 
 pytestmark = pytest.mark.gpu
@@ -20,13 +21,13 @@ def _both(tok, dout, V, D, p, accumulate, init):
     ctr = torch.tensor([5], dtype=torch.int64, device=DEV)
     out = []
     for csr in (True, False):
-        kk.EMBED_CSR = csr
+        embedding.EMBED_CSR = csr
         try:
             dt = init.clone()
             kk.embed_bwd(tok, dout, dt, math.sqrt(D), p, 99, ctr, 4, accumulate=accumulate)
             out.append(dt)
         finally:
-            kk.EMBED_CSR = True
+            embedding.EMBED_CSR = True
     torch.cuda.synchronize()
     return out
 

@@ -42,11 +42,11 @@ def _batches(dev):
 
 def _run(dev, graph, ddp_factory=None, fp8=False, select_margin=None):
     from tensorflow_distributed_on_gke_amd.models.transformer import Transformer, model_config
-    from tensorflow_distributed_on_gke_amd.ops import kernels as kk
+    from tensorflow_distributed_on_gke_amd.ops import tuning
     from tensorflow_distributed_on_gke_amd.train.optim import Adam
     from tensorflow_distributed_on_gke_amd.train.step import TrainStep
 
-    kk.AUTOTUNE = False  # identical GEMM configs in both runs
+    tuning.AUTOTUNE = False  # identical GEMM configs in both runs
     cfg = model_config("tiny", d_model=256, heads=4, d_ff=1024, src_vocab=500, tgt_vocab=400, dropout=0.1)
     m = Transformer(cfg).build(dev, seed=3)
     opt = Adam(m.store, cfg.d_model, lr=0.003)

@@ -7,6 +7,7 @@ import torch
 
 import ref_tail as R
 from tensorflow_distributed_on_gke_amd.ops import kernels as kk
+from tensorflow_distributed_on_gke_amd.ops.kernels import layernorm
 from tensorflow_distributed_on_gke_amd.ops import philox
 
 pytestmark = pytest.mark.gpu
@@ -335,7 +336,8 @@ def test_attention_probs():
 @pytest.mark.parametrize("p", [0.0, 0.1])
 @pytest.mark.parametrize("rpb", [16, 32, 64])
 def test_add_ln_fwd_bwd(D, p, rpb, monkeypatch):
-    monkeypatch.setattr(kk, "LN_BWD_RPB", rpb)  # rows per backward workgroup
+    monkeypatch.setattr(layernorm, "LN_BWD_RPB", rpb)  # rows per backward workgroup
+    assert kk.ln_bwd_rpb(D) == rpb
     M = 300
     seed, site = 1234, 7
     ctr = torch.tensor([5], dtype=torch.int64)

@@ -153,11 +153,11 @@ def _long_batches(dev, B, S, T, n):
 
 def _train(graph, fp8, steps=2, B=4, L=1000):
     from tensorflow_distributed_on_gke_amd.models.transformer import Transformer, model_config
-    from tensorflow_distributed_on_gke_amd.ops import kernels as kk
+    from tensorflow_distributed_on_gke_amd.ops import tuning
     from tensorflow_distributed_on_gke_amd.train.optim import Adam
     from tensorflow_distributed_on_gke_amd.train.step import TrainStep
 
-    kk.AUTOTUNE = False  # identical GEMM configs in both runs
+    tuning.AUTOTUNE = False  # identical GEMM configs in both runs
     cfg = model_config("base")
     m = Transformer(cfg).build(DEV, seed=2)
     opt = Adam(m.store, cfg.d_model)

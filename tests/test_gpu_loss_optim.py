@@ -12,6 +12,7 @@ import torch
 import ref_tail as R
 from ref_tail import BF16, F32, F64, AdamCfg
 from tensorflow_distributed_on_gke_amd.ops import kernels as kk
+from tensorflow_distributed_on_gke_amd.ops._ext import C
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -361,7 +362,7 @@ def test_adam_capped_grid():
 def test_to_bf16(n):
     x = R.to_bf16_inputs(n)
     o = torch.full((n + 8,), 3.0, dtype=BF16, device=DEV)
-    kk.C().to_bf16(x.to(DEV), o[:n])
+    C().to_bf16(x.to(DEV), o[:n])
     torch.cuda.synchronize()
     R.exact(o[:n], x.to(BF16), f"to_bf16 n={n}")
     assert bool((o[n:] == 3.0).all())

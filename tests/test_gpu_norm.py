@@ -27,6 +27,7 @@ import ref_norm as N
 import ref_tail as R
 from ref_norm import BF16
 from tensorflow_distributed_on_gke_amd.ops import kernels as kk
+from tensorflow_distributed_on_gke_amd.ops.kernels import layernorm
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -119,7 +120,8 @@ def _same(a, b, what, keys=("dh", "ds", "dgamma", "dbeta", "dbias")):
 @pytest.mark.parametrize("rpb", N.RPBS)
 @pytest.mark.parametrize("D", N.DS)
 def test_ln_bwd(D, rpb, monkeypatch):
-    monkeypatch.setattr(kk, "LN_BWD_RPB", rpb)  # rows per backward workgroup
+    monkeypatch.setattr(layernorm, "LN_BWD_RPB", rpb)  # rows per backward workgroup
+    assert kk.ln_bwd_rpb(D) == rpb
     old = {k: torch.full((D,), OLD) for k in ("dgamma", "dbeta", "dbias")}
     for c in N.bwd_cases(D, rpb):
         i = N.bwd_inputs(D, c.M, c.p, c.dres)
@@ -194,14 +196,14 @@ def _fold_items(beta, off):
 @pytest.mark.parametrize("beta", [0.0, 1.0])
 def test_reduce_partials_multi_past_96(beta, arm, off, monkeypatch):
     """100 items of one (N, beta): two launches through the wrapper's chunks."""
-    real, launches = kk.C(), []
+    real, launches = layernorm.C(), []
 
     class Spy:
         def reduce_partials_multi(self, parts, *rest):
             launches.append(len(parts))
             return real.reduce_partials_multi(parts, *rest)
 
-    monkeypatch.setattr(kk, "C", lambda: Spy())
+    monkeypatch.setattr(layernorm, "C", lambda: Spy())  # where ln_bwd / reduce_partials_multi look it up
     items = _fold_items(beta, off)
     kk.reduce_partials_multi(items)
     torch.cuda.synchronize()
@@ -214,8 +216,8 @@ def test_reduce_partials_multi_refuses_97():
     items = _fold_items(1.0, 0)[:97]
     before = [it[1].clone() for it in items]
     with pytest.raises(RuntimeError):
-        kk.C().reduce_partials_multi([it[0] for it in items], [it[1] for it in items], [it[2] for it in items],
-                                     N.FOLD_N, 1.0)
+        layernorm.C().reduce_partials_multi([it[0] for it in items], [it[1] for it in items],
+                                            [it[2] for it in items], N.FOLD_N, 1.0)
     torch.cuda.synchronize()
     for it, b in zip(items, before):
         R.exact(it[1], b, "output after the refused call")
