@@ -20,16 +20,15 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from tensorflow_distributed_on_gke_amd.models.layers import (_dgrad_res, _wgrad,
-                                                              CrossAttnBlockFn, CrossKVFn, EmbedFn,
+from tensorflow_distributed_on_gke_amd.models.layers import (CrossAttnBlockFn, CrossKVFn, EmbedFn,
                                                               FFNBlockFn, KVGrad, RunCtx,
                                                               SelfAttnBlockFn)
+from tensorflow_distributed_on_gke_amd.models.loss_head import (  # noqa: F401 (PAD_ID: re-exported)
+    PAD_ID, cpu_head, gpu_head)
 from tensorflow_distributed_on_gke_amd.models.params import (ParamStore, TFSlot, const,
                                                               glorot_blocks, glorot_uniform,
                                                               uniform)
 from tensorflow_distributed_on_gke_amd.ops import kernels as K
-
-PAD_ID = 0
 
 
 @dataclass
@@ -331,16 +330,15 @@ class Transformer:
         distill = teacher is not None and alpha > 0.0
         if distill and rt.fp8 is not None:
             raise ValueError("loss_and_backward: distillation is not supported with dtype=fp8")
-        cfg = self.cfg
         dev = src.device
-        if dev.type == "cuda":  # split / lengths / token count / ctr: one launch
+        gpu = dev.type == "cuda"
+        ntok = ntok_work = None
+        if gpu:  # split / lengths / token count / ctr: one launch
             tgt_in, labels, src_len, tgt_len, ntok = K.prep_batch(
                 src, tgt, rt.ctr if bump_ctr else None)
             lengths = (src_len, tgt_len)
             # the label count all-reduce flies during the forward
             ntok_work = ntok_sum(ntok) if ntok_sum is not None else None
-            if ntok_total is not None:
-                ntok = ntok_total
         else:
             if bump_ctr:
                 rt.ctr.add_(1)
@@ -348,86 +346,21 @@ class Transformer:
             labels = tgt[:, 1:].contiguous()
             lengths = None
         B, T = tgt_in.shape
-        M = B * T
         t_logits = teacher.logits(src, tgt_in, lengths) if distill else None
         if step_out is None:
             step_out = torch.zeros(2, dtype=torch.float32, device=dev)
         grad_ctx = torch.enable_grad() if backward else torch.no_grad()
         with grad_ctx:
             dec = self.features(src, tgt_in, rt, lengths)
-        dec2 = dec.detach().reshape(M, cfg.d_model)
-        if dev.type == "cuda":
-            logits = self.project(dec.detach())
-            row_loss = K.workspace("row_loss", M, dev)[:M]
-            row_cor = K.workspace("row_correct", M, dev)[:M]
-            if ntok_work is not None:
-                ntok_work.wait()
-            if distill:
-                row_lab = K.workspace("row_label", M, dev)[:M]
-                K.xent_distill(logits, t_logits, cfg.tgt_vocab, labels, ntok, workers,
-                               cfg.label_smoothing, alpha, teacher.weights, row_loss, row_cor,
-                               row_lab, write_grad=backward)
-                if label_accum is not None:
-                    K.xent_stats(row_lab, row_cor, ntok, workers, None, label_accum)
-            else:
-                K.xent(logits, cfg.tgt_vocab, labels, ntok, workers, cfg.label_smoothing, row_loss,
-                       row_cor, write_grad=backward)
-            K.xent_stats(row_loss, row_cor, ntok, workers, step_out, accum)
-            if not backward:
-                return step_out
-            beta = 1.0 if rt.accumulate else 0.0
-            dl = logits  # now holds dlogits (pad columns zeroed)
-            _wgrad(rt, dl, dec2.contiguous(), cfg.tgt_vocab, self.final.w, self.final.b)
-            ddec = _dgrad_res(dl, self.final.w, cfg.tgt_vocab, None)
+        if gpu:
+            ddec = gpu_head(self, rt, dec, labels, ntok, ntok_work, ntok_total, workers, step_out,
+                            accum, label_accum, backward, t_logits, teacher, alpha)
         else:
-            lg = self.project(dec.detach())
-            lab = labels.reshape(-1)
-            mask = (lab != PAD_ID).to(torch.float32)
-            ntok = mask.sum() if ntok_total is None else ntok_total.reshape(()).clone()
-            if ntok_sum is not None:
-                w = ntok_sum(ntok)
-                if w is not None:
-                    w.wait()
-            ntok = ntok.clamp_min(1.0)
-            logp = torch.log_softmax(lg, dim=-1)
-            eps = cfg.label_smoothing
-            nll = -logp.gather(1, lab.view(-1, 1)).squeeze(1)
-            smooth = -logp.mean(dim=-1)
-            row_loss = ((1 - eps) * nll + eps * smooth) * mask
-            if distill:
-                label_loss = row_loss.sum() / ntok / workers
-                target = K.distill_target(t_logits, cfg.tgt_vocab, lab, eps, alpha, teacher.weights)
-                row_loss = -(target * logp).sum(dim=-1) * mask
-            correct = ((lg.argmax(dim=-1) == lab).to(torch.float32) * mask).sum()
-            loss = row_loss.sum() / ntok / workers
-            acc = correct / ntok
-            if distill and label_accum is not None:
-                label_accum += torch.stack([label_loss, acc, torch.tensor(1.0), ntok])
-            step_out.copy_(torch.stack([loss, acc]).detach())
-            if accum is not None:
-                accum += torch.stack([loss.detach(), acc.detach(), torch.tensor(1.0), ntok])
-            if not backward:
-                return step_out
-            if distill:
-                dl = torch.softmax(lg, -1) - target
-            else:
-                onehot = torch.nn.functional.one_hot(lab, cfg.tgt_vocab).to(torch.float32)
-                dl = (torch.softmax(lg, -1) - (1 - eps) * onehot - eps / cfg.tgt_vocab)
-            dl = dl * (mask / (ntok * workers)).view(-1, 1)
-            fw, fb = self.final.w, self.final.b
-            g_w = dl.t() @ dec2
-            g_b = dl.sum(0)
-            if rt.accumulate:
-                fw.grad.add_(g_w)
-                fb.grad.add_(g_b)
-            else:
-                fw.grad.copy_(g_w)
-                fb.grad.copy_(g_b)
-            if rt.store is not None:
-                rt.store.grad_ready(fw)
-                rt.store.grad_ready(fb)
-            ddec = dl @ fw.master
-        dec.backward(ddec.view(B, T, cfg.d_model).to(dec.dtype))
+            ddec = cpu_head(self, rt, dec, labels, ntok_sum, ntok_total, workers, step_out,
+                            accum, label_accum, backward, t_logits, teacher, alpha)
+        if ddec is None:
+            return step_out
+        dec.backward(ddec.view(B, T, self.cfg.d_model).to(dec.dtype))
         if rt.wgrad is not None:
             rt.wgrad.flush()
             rt.wgrad.step_done()

@@ -1,7 +1,8 @@
 """A training step as a chain of HIP graphs cut at its host-issued collectives.
 
 The data-parallel step cannot be one plain graph replay without putting the
-RCCL collectives inside the capture (TDG_DP_GRAPH=full, see TrainStep), and
+RCCL collectives inside the capture (round 1's TDG_DP_GRAPH=full, which failed
+capture under PyTorch 2.10's process-group watchdog and was removed), and
 running it eagerly costs ~5-6 ms of host enqueue per step for ~5.5 ms of GPU
 work (docs/ROADMAP.md item 5): each rank is launch-bound. The segmented graph
 keeps the collectives as ordinary eager `torch.distributed` calls and captures

@@ -21,8 +21,6 @@ replicas only when the host reads it (log points).
 from __future__ import annotations
 
 import os
-import time
-from collections import OrderedDict
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -31,11 +29,11 @@ import torch.distributed as dist
 from tensorflow_distributed_on_gke_amd.config import check_accum_steps
 from tensorflow_distributed_on_gke_amd.models.layers import RunCtx, WgradQueue
 from tensorflow_distributed_on_gke_amd.models.transformer import Transformer
-from tensorflow_distributed_on_gke_amd.parallel import ddp as _ddp_mod
 from tensorflow_distributed_on_gke_amd.parallel.ddp import DataParallel
 from tensorflow_distributed_on_gke_amd.ops import kernels as K
 from tensorflow_distributed_on_gke_amd.train.graphs import SegmentedGraph, prepare_capture
 from tensorflow_distributed_on_gke_amd.train.optim import Adam
+from tensorflow_distributed_on_gke_amd.train.step_cache import Captured, StepCache
 
 
 # data parallel: weight gradients flushed in wave-sized chunks at layer ends
@@ -165,9 +163,6 @@ class TrainStep:
         # distillation: the label cross entropy alone, same four slots as accum
         self.label_accum = (torch.zeros(4, dtype=torch.float32, device=dev)
                             if self.teacher is not None else None)
-        self.graph = None
-        self.segments: Optional[SegmentedGraph] = None
-        self._static: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
         # Variable-length batches (text data, the reference's padded-to-the-
         # batch-max shapes: english_portugese_dataset.py:44-46, __main__.py:127
         # experimental_relax_shapes): with `bucketed` set, a batch of a shape
@@ -177,19 +172,22 @@ class TrainStep:
         # them allocate from ONE memory pool: each replay is a whole step, so
         # the intermediates of different shapes may share memory (workspaces,
         # which persist, are never reused: ops.kernels.workspace).
-        self.bucketed = False
-        self.graph_cache = 64
-        self._graphs: "OrderedDict[tuple, tuple]" = OrderedDict()
-        self._key: Optional[tuple] = None
-        self._pos = "only"  # the current captured micro-batch's position
+        self.cache = StepCache(capacity=64, bucketed=False)
         self._pool = None
         self._cap_stream: Optional[torch.cuda.Stream] = None
         self._warm_stream: Optional[torch.cuda.Stream] = None
-        self.graph_stats = {"captures": 0, "replays": 0, "evictions": 0}
 
-    @property
-    def captured(self) -> bool:
-        return self.graph is not None or self.segments is not None or bool(self._graphs)
+    # the captured steps (train/step_cache.py) under the names callers read
+    graph = property(lambda self: self.cache.entry.graph)
+    segments = property(lambda self: self.cache.entry.segments)
+    captured = property(lambda self: bool(self.cache.entries))
+    cached_shapes = property(lambda self: len(self.cache.entries))
+    _graphs = property(lambda self: self.cache.entries)  # (read-only: the name before the cache)
+    graph_stats = property(lambda self: self.cache.stats)
+    bucketed = property(lambda self: self.cache.bucketed,
+                        lambda self, v: setattr(self.cache, "bucketed", v))
+    graph_cache = property(lambda self: self.cache.capacity,
+                           lambda self, v: setattr(self.cache, "capacity", v))
 
     def capture_mode(self) -> str:
         """"single" (one graph, no collectives), "seg" or "0" (the
@@ -357,8 +355,7 @@ class TrainStep:
         mode = self.capture_mode()
         if self._pool is None:
             self._pool = torch.cuda.graph_pool_handle()
-        # (no current entry until this one is registered)
-        self.graph = self.segments = self._static = self._key = None
+        self.cache.clear_current()  # (no current entry until this one is put)
         static = (src.clone(), tgt.clone())
         saved = self.snapshot()
         if self._cap_stream is None:
@@ -381,6 +378,7 @@ class TrainStep:
             self.ddp.check_quiescent("capture")
             dist.barrier(group=self.ddp.group)
             torch.cuda.synchronize()
+        g = rec = None
         if mode == "seg":
             prepare_capture()
             cap = self._cap_stream
@@ -398,12 +396,11 @@ class TrainStep:
             finally:
                 self.ddp.recorder = None
             torch.cuda.current_stream().wait_stream(cap)
-            self._register(None, rec, static, pos)
-            return
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, pool=self._pool, stream=self._cap_stream):
-            self.eager(*static, pos)
-        self._register(g, None, static, pos)
+        else:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=self._pool, stream=self._cap_stream):
+                self.eager(*static, pos)
+        self.cache.put(self._cache_key(src.shape, tgt.shape, pos), Captured(g, rec, static))
 
     # ------------------------------------------------------------------ shape cache
     def _cache_key(self, src_shape, tgt_shape, pos: str) -> tuple:
@@ -412,182 +409,42 @@ class TrainStep:
         global token mean) and where the label count comes from."""
         return (tuple(src_shape), tuple(tgt_shape), pos, self.workers, self.global_mean)
 
-    def _register(self, graph, segments, static, pos: str) -> None:
-        """The just-captured micro-batch becomes the current cache entry."""
-        self.graph, self.segments, self._static, self._pos = graph, segments, static, pos
-        self._key = self._cache_key(static[0].shape, static[1].shape, pos)
-        self._graphs[self._key] = (graph, segments, static)
-        self._graphs.move_to_end(self._key)
-        self.graph_stats["captures"] += 1
-
-    @property
-    def cached_shapes(self) -> int:
-        return len(self._graphs)
-
-    def _install(self, entries) -> None:
-        """Replace the cache by `entries` (none: the step runs eagerly)."""
-        self._graphs = OrderedDict(entries or ())
-        self.graph = self.segments = None
-        self._static = None
-        self._key = None
-        if self._graphs:  # the newest entry is current
-            key = next(reversed(self._graphs))
-            self.graph, self.segments, self._static = self._graphs[key]
-            self._key, self._pos = key, key[2]
-
-    def _select(self, src: torch.Tensor, tgt: torch.Tensor, pos: str = "only") -> None:
+    def _select(self, key: tuple, src: torch.Tensor, tgt: torch.Tensor) -> None:
         """Make the captured micro-batch of this batch shape and position
         current: a cache hit, or (bucketed) a capture on the spot, evicting
         the least recently used one when the cache is full. Every rank sees
         the same global-batch shapes in the same order, so every rank
         captures and evicts alike."""
-        key = self._cache_key(src.shape, tgt.shape, pos)
-        if key == self._key:
+        cache = self.cache
+        if cache.get(key) is not None:
             return
-        ent = self._graphs.get(key)
-        if ent is not None:
-            self._graphs.move_to_end(key)
-            self.graph, self.segments, self._static = ent
-            self._key, self._pos = key, pos
-            return
-        if not self.bucketed:
-            shapes = sorted({(k[0], k[1]) for k in self._graphs})
-            raise ValueError(f"captured step takes {' or '.join(f'{a} / {b}' for a, b in shapes)} "
+        if not cache.bucketed:
+            raise ValueError(f"captured step takes {' or '.join(f'{a} / {b}' for a, b in cache.shapes())} "
                              f"batches, got {tuple(src.shape)} / {tuple(tgt.shape)}")
-        while len(self._graphs) >= max(1, self.graph_cache):
-            self._graphs.popitem(last=False)
-            self.graph_stats["evictions"] += 1
+        cache.make_room()
         if self.capture_mode() == "0":
             raise RuntimeError("bucketed step: capture of a new batch shape failed")
-        self._capture_micro(src, tgt, pos, warmup=1)
+        self._capture_micro(src, tgt, key[2], warmup=1)
 
     def _replay(self, src: torch.Tensor, tgt: torch.Tensor, pos: str) -> None:
-        st = self._static
-        if st is None or pos != self._pos or src.shape != st[0].shape or tgt.shape != st[1].shape:
-            self._select(src, tgt, pos)
-            st = self._static
-        self.graph_stats["replays"] += 1
-        st[0].copy_(src, non_blocking=True)
-        st[1].copy_(tgt, non_blocking=True)
-        if self.segments is not None:
-            self.segments.replay()
+        key = self._cache_key(src.shape, tgt.shape, pos)
+        if key != self.cache.current:
+            self._select(key, src, tgt)
+        graph, segments, static = self.cache.entry
+        self.cache.stats["replays"] += 1
+        static[0].copy_(src, non_blocking=True)
+        static[1].copy_(tgt, non_blocking=True)
+        if segments is not None:
+            segments.replay()
         else:
-            self.graph.replay()
+            graph.replay()
 
     def choose_dp_mode(self, src: torch.Tensor, tgt: torch.Tensor, steps: int = 8,
                        rounds: int = 3, margin: float = 0.03) -> Dict[str, object]:
-        """Data parallel: pick how the step runs on THIS node, by measurement.
-
-        Arms: the segmented graph (collectives issued between graph segments)
-        and the eager step; and, where a comm thread exists
-        (ddp.COMM_THREAD "auto"), both once more with the collectives issued
-        by the host comm thread instead of the process group's own stream
-        handoff. With accum_steps > 1 every arm runs whole updates (the batch
-        repeated as each micro-batch). Each arm is timed in interleaved rounds
-        (median per arm, MAX over ranks, so every rank takes the same
-        decision) and, after its timed steps, the replicas must be bitwise
-        equal (DataParallel.verify_replicas raises otherwise: an issue path
-        that breaks synchronous DP is an error, not a slower option). The
-        segmented graph wins when the host is the bottleneck (eight ranks
-        sharing a node's CPUs); the eager step when the host keeps ahead. The
-        training state is restored afterwards, so this trains nothing.
-        Without a measurement (the step is not captured, DP_AUTOSELECT off)
-        an available comm thread is used. Returns {"mode": "seg" | "0",
-        "comm_thread": bool, "reason": "measured" | "unmeasured",
-        "<arm>_ms": .., "select_s": seconds this selection took}."""
-        ddp = self.ddp
-        t_start = time.perf_counter()
-        auto_thread = (ddp is not None and ddp.active and ddp.can_thread
-                       and _ddp_mod.COMM_THREAD == "auto")
-        if auto_thread:
-            ddp.use_thread(False)
-
-        def unmeasured(mode: str) -> Dict[str, object]:
-            # no start-up measurement: with a comm thread available ("auto")
-            # the thread issues the collectives -- it won the one-rank RCCL A/B
-            # on MI355X for the eager and the segmented step alike (5.11 vs
-            # 5.34 ms, profiles/r4/ab_dp_comm_thread.txt)
-            if auto_thread:
-                ddp.use_thread(True)
-            th = ddp is not None and ddp._thread is not None
-            return {"mode": mode, "comm_thread": th, "reason": "unmeasured",
-                    "select_s": round(time.perf_counter() - t_start, 3)}
-
-        if not self.capture(src, tgt):
-            return unmeasured(self.capture_mode())
-        if not (ddp is not None and ddp.active and self.segments is not None) or not DP_AUTOSELECT:
-            return unmeasured("seg" if self.segments is not None else self.capture_mode())
-        # an arm: the captured micro-batches of one update (cache entries)
-        arms = {"seg": (dict(self._graphs), ddp._thread is not None)}
-        if auto_thread:
-            self._install(None)
-            ddp.use_thread(True)
-            if self.capture(src, tgt):
-                arms["seg_thread"] = (dict(self._graphs), True)
-            ddp.use_thread(False)
-        saved = self.snapshot()
-        micro = [(src, tgt)] * self.accum_steps
-        dev = self.model.device
-
-        def timed(run) -> float:
-            for _ in range(2):
-                run()
-            torch.cuda.synchronize()
-            ddp.check_quiescent("choose_dp_mode")
-            dist.barrier(group=ddp.group)
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                run()
-            torch.cuda.synchronize()
-            dt = (time.perf_counter() - t0) / steps
-            ddp.verify_replicas()  # the arm kept synchronous DP exact
-            return dt
-
-        def run():
-            self.update(micro)
-
-        # eager arms: the process group's handoff, and (auto) the comm thread
-        eager_arms = {"0": False}
-        if auto_thread:
-            eager_arms["0_thread"] = True
-        names = list(arms) + list(eager_arms)
-        runs = {k: [] for k in names}
-        for _ in range(rounds):
-            for k in names:
-                if k in eager_arms:
-                    self._install(None)
-                    ddp.use_thread(eager_arms[k])
-                else:
-                    self._install(arms[k][0])
-                    ddp.use_thread(arms[k][1])  # (a captured graph keeps its own path)
-                runs[k].append(timed(run))
-        # median per arm: one noisy round (box clock, host contention) does
-        # not decide the mode for the whole run
-        med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
-        t = torch.tensor([med[k] for k in names], dtype=torch.float64, device=dev)
-        ddp.check_quiescent("choose_dp_mode")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=ddp.group)
-        ms = {k: float(v) for k, v in zip(names, t.tolist())}
-        self.restore(saved)
-        best_seg = min((k for k in names if k not in eager_arms), key=lambda k: ms[k])
-        best_eager = min(eager_arms, key=lambda k: ms[k])
-        if ms[best_eager] < ms[best_seg] * (1.0 - margin):
-            self._install(None)
-            th = eager_arms[best_eager]
-            ddp.use_thread(th)
-            mode = "0"
-        else:
-            self._install(arms[best_seg][0])
-            th = arms[best_seg][1]
-            ddp.use_thread(th)
-            mode = "seg"
-        arms.clear()  # the other captures' graphs are released
-        torch.cuda.synchronize()
-        out = {"mode": mode, "comm_thread": th, "reason": "measured"}
-        out.update({f"{k.replace('0', 'eager', 1) if k.startswith('0') else k}_ms": round(v * 1e3, 3)
-                    for k, v in ms.items()})
-        out["select_s"] = round(time.perf_counter() - t_start, 3)
-        return out
+        """Data parallel: pick how the step runs on THIS node, by measurement
+        (train/dp_select.py has the arms, the rule and the returned record)."""
+        from tensorflow_distributed_on_gke_amd.train.dp_select import choose_dp_mode
+        return choose_dp_mode(self, src, tgt, steps, rounds, margin)
 
     def __call__(self, src: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
         if self.accum_steps != 1:

@@ -200,7 +200,7 @@ def test_captured_micro_batches_equal_eager_bitwise(loss_mode):
     f_g, l_g, a_g, st = _run_updates(updates, True, loss_mode)
     assert st.captured and st.graph_stats["replays"] == 12
     # one graph per (shape, position) seen: a first/middle/last, b first/middle/last
-    keys = sorted((k[0], k[2]) for k in st._graphs)
+    keys = sorted((k[0], k[2]) for k in st.cache.entries)
     assert keys == sorted(((B, S), pos) for (B, S, _) in ((4, 32, 33), (3, 40, 25))
                           for pos in ("first", "middle", "last")), keys
     assert st.graph_stats["captures"] == 6 and st.graph_stats["evictions"] == 0
@@ -216,7 +216,7 @@ def test_one_micro_batch_keeps_one_graph_per_shape():
     f_e, l_e, _, _ = _run_updates(updates, False, "replica_mean", accum_steps=1)
     f_g, l_g, _, st = _run_updates(updates, True, "replica_mean", accum_steps=1)
     assert st.cached_shapes == 2 and st.graph_stats["captures"] == 2
-    assert {k[2] for k in st._graphs} == {"only"}
+    assert {k[2] for k in st.cache.entries} == {"only"}
     assert torch.equal(l_e, l_g) and torch.equal(f_e, f_g)
 
 
@@ -250,8 +250,8 @@ def test_text_training_loop_accumulates_bucketed_micro_batches(tmp_path):
     st = tr.step_fn
     assert st.captured and st.bucketed and st.global_mean
     assert st.graph_stats["replays"] == 3 * tr.global_step
-    assert {k[2] for k in st._graphs} == {"first", "middle", "last"}
-    assert len({(k[0], k[1]) for k in st._graphs}) > 1  # more than one bucket shape
+    assert {k[2] for k in st.cache.entries} == {"first", "middle", "last"}
+    assert len({(k[0], k[1]) for k in st.cache.entries}) > 1  # more than one bucket shape
     assert hist and hist[0].train_loss == hist[0].train_loss and 0 < hist[0].train_loss < 20
     assert 0.0 <= hist[0].train_acc <= 1.0
 
@@ -324,7 +324,7 @@ def _dp_worker(rank, world, port, out, loss_mode, graph, comm_thread):
     calls = {}
     if graph:
         assert step.captured
-        for k, (_, segs, _) in step._graphs.items():
+        for k, (_, segs, _) in step.cache.entries.items():
             calls.setdefault(k[2], []).append(segs.num_calls)
     torch.save({"flat": m.store.flat.cpu(), "loss": torch.stack(losses), "nb": len(ddp.last_buckets),
                 "early": early, "calls": calls}, f"{out}.{rank}")
@@ -390,7 +390,7 @@ def _select_worker(rank, port, out):
             assert sel["seg_ms"] > 0 and sel["eager_ms"] > 0, sel
             assert step.captured == (name == "sel_seg")
             if step.captured:
-                assert sorted(k[2] for k in step._graphs) == ["first", "last"]
+                assert sorted(k[2] for k in step.cache.entries) == ["first", "last"]
         for mbs in updates:
             step.update(mbs)
         torch.cuda.synchronize()

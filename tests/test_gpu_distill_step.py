@@ -84,7 +84,7 @@ def _run(accum_steps, graph, updates=3):
         torch.cuda.synchronize()
         assert opt.iterations == 0 and float(step.accum.abs().sum()) == 0  # capture() trains nothing
         assert float(step.label_accum.abs().sum()) == 0
-        assert sorted(k[2] for k in step._graphs) == (["only"] if accum_steps == 1 else ["first", "last"])
+        assert sorted(k[2] for k in step.cache.entries) == (["only"] if accum_steps == 1 else ["first", "last"])
     shares = []
     for mbs in batches:
         step.update(mbs)
