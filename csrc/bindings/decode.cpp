@@ -1,8 +1,9 @@
 // Decoding bindings: single-query attention over an indexed K/V cache and the
-// beam-search selection and sampling steps and the ensemble's probability
-// average (decode.hip).
+// beam-search selection and sampling steps, the ensemble's probability
+// average and teacher-forced scoring (decode.hip).
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 
 #include "common.h"
 
@@ -194,8 +195,32 @@ void sample_token(const Tensor& logits, int64_t V, const Tensor& score, const Te
   check_err(tdg_sample_token(&a, stream_of(logits)), "tdg sample_token");
 }
 
-// weights: the members' mixture weights, > 0 (the Python wrapper normalises
-// them to sum 1); the kernel gets their logarithms
+// The members of a mixture (EnsembleArgs / ScoreArgs): M bf16 tensors [R, >= V]
+// on `dev`, each with its own row stride, and their weights, > 0 (the Python
+// wrapper normalises them to sum 1); the kernel gets their logarithms.
+void check_members(const std::vector<Tensor>& logits, int64_t V, const std::vector<double>& weights,
+                   int64_t R, const c10::Device& dev, const char* op, const uint16_t** x, int* ldls,
+                   float* logw) {
+  const int64_t M = (int64_t)logits.size();
+  for (int64_t m = 0; m < M; ++m) {
+    const Tensor& t = logits[m];
+    check_bf16(t, "logits");
+    TORCH_CHECK(t.device() == dev, op, ": members and outputs on one device");
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == R && t.stride(1) == 1 && t.size(1) >= V,
+                "every member's logits must be [R, >= V], rows contiguous");
+    const int64_t ldl = t.stride(0);
+    TORCH_CHECK(ldl < (1LL << 31) && ldl % 8 == 0 && (ldl >= round8(V) || R <= 1), op,
+                ": logits row stride must be a multiple of 8");
+    check_aligned(t, 16, "logits");
+    check_extent(t, R, ldl, round8(V), "logits");
+    TORCH_CHECK(std::isfinite(weights[m]) && weights[m] > 0 && std::isfinite(std::log(weights[m])),
+                op, ": weights must be finite and > 0, got ", weights[m]);
+    x[m] = (const uint16_t*)t.data_ptr();
+    ldls[m] = (int)ldl;
+    logw[m] = (float)std::log(weights[m]);
+  }
+}
+
 void ensemble_logprobs(const std::vector<Tensor>& logits, int64_t V,
                        const std::vector<double>& weights, const Tensor& out) {
   const int64_t M = (int64_t)logits.size();
@@ -214,23 +239,7 @@ void ensemble_logprobs(const std::vector<Tensor>& logits, int64_t V,
   check_aligned(out, 16, "out");
   check_extent(out, R, ldo, No, "out");
   tdg::EnsembleArgs a{};
-  for (int64_t m = 0; m < M; ++m) {
-    const Tensor& x = logits[m];
-    check_bf16(x, "logits");
-    TORCH_CHECK(x.device() == out.device(), "ensemble_logprobs: members and out on one device");
-    TORCH_CHECK(x.dim() == 2 && x.size(0) == R && x.stride(1) == 1 && x.size(1) >= V,
-                "every member's logits must be [R, >= V], rows contiguous");
-    const int64_t ldl = x.stride(0);
-    TORCH_CHECK(ldl < (1LL << 31) && ldl % 8 == 0 && (ldl >= round8(V) || R <= 1),
-                "ensemble_logprobs: logits row stride must be a multiple of 8");
-    check_aligned(x, 16, "logits");
-    check_extent(x, R, ldl, round8(V), "logits");
-    TORCH_CHECK(std::isfinite(weights[m]) && weights[m] > 0 && std::isfinite(std::log(weights[m])),
-                "ensemble_logprobs: weights must be finite and > 0, got ", weights[m]);
-    a.x[m] = (const uint16_t*)x.data_ptr();
-    a.ldl[m] = (int)ldl;
-    a.logw[m] = (float)std::log(weights[m]);
-  }
+  check_members(logits, V, weights, R, out.device(), "ensemble_logprobs", a.x, a.ldl, a.logw);
   a.out = (uint16_t*)out.data_ptr();
   a.M = (int)M;
   a.R = (int)R;
@@ -239,6 +248,47 @@ void ensemble_logprobs(const std::vector<Tensor>& logits, int64_t V,
   a.No = (int)No;
   c10::DeviceGuard g(out.device());
   check_err(tdg_ensemble_logprobs(&a, stream_of(out)), "tdg ensemble_logprobs");
+}
+
+// labels: int32 or int64 [R]; tok_lp and (optional) top_lp: f32 [R]; all on
+// the members' device, R the members' row count
+void score_tokens(const std::vector<Tensor>& logits, int64_t V, const std::vector<double>& weights,
+                  const Tensor& labels, int64_t pad_id, const Tensor& tok_lp,
+                  const optional<Tensor>& top_lp) {
+  const int64_t M = (int64_t)logits.size();
+  TORCH_CHECK(M >= 1 && M <= tdg::ENSEMBLE_MAX, "score_tokens: 1 to ", tdg::ENSEMBLE_MAX,
+              " members, got ", M);
+  TORCH_CHECK((int64_t)weights.size() == M, "score_tokens: ", weights.size(), " weights for ", M,
+              " members");
+  TORCH_CHECK(V >= 1 && V <= 65536, "score_tokens: V must be in [1, 65536], got ", V);
+  TORCH_CHECK(logits[0].dim() == 2, "every member's logits must be [R, >= V], rows contiguous");
+  const int64_t R = logits[0].size(0);
+  TORCH_CHECK(R < (1LL << 31), "score_tokens: too many rows");
+  TORCH_CHECK(logits[0].is_cuda(), "logits must be a GPU tensor");
+  const c10::Device dev = logits[0].device();
+  const auto lt = labels.scalar_type();
+  TORCH_CHECK(lt == at::kInt || lt == at::kLong, "labels must be int32 or int64");
+  TORCH_CHECK(labels.device() == dev && labels.dim() == 1 && labels.numel() == R &&
+                  labels.is_contiguous(),
+              "labels must be [R] on the members' device");
+  TORCH_CHECK(pad_id >= INT32_MIN && pad_id <= INT32_MAX, "score_tokens: pad_id");
+  for (const Tensor* o : {&tok_lp, top_lp.has_value() ? &*top_lp : &tok_lp}) {
+    check_f32(*o, "tok_lp / top_lp");
+    TORCH_CHECK(o->device() == dev && o->dim() == 1 && o->numel() == R && o->is_contiguous(),
+                "tok_lp / top_lp must be f32 [R] on the members' device");
+  }
+  tdg::ScoreArgs a{};
+  check_members(logits, V, weights, R, dev, "score_tokens", a.x, a.ldl, a.logw);
+  a.labels = labels.data_ptr();
+  a.lab64 = lt == at::kLong ? 1 : 0;
+  a.tok_lp = tok_lp.data_ptr<float>();
+  a.top_lp = opt_f32(top_lp);
+  a.M = (int)M;
+  a.R = (int)R;
+  a.V = (int)V;
+  a.pad_id = (int)pad_id;
+  c10::DeviceGuard g(dev);
+  check_err(tdg_score_tokens(&a, stream_of(tok_lp)), "tdg score_tokens");
 }
 
 }  // namespace
@@ -259,4 +309,6 @@ void def_decode(py::module_& m) {
         py::arg("score_out"), py::arg("token"), py::arg("fin_out"));
   m.def("ensemble_logprobs", &ensemble_logprobs, py::arg("logits"), py::arg("V"),
         py::arg("weights"), py::arg("out"));
+  m.def("score_tokens", &score_tokens, py::arg("logits"), py::arg("V"), py::arg("weights"),
+        py::arg("labels"), py::arg("pad_id"), py::arg("tok_lp"), py::arg("top_lp") = py::none());
 }

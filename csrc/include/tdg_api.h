@@ -53,12 +53,13 @@ int tdg_attn_bwd_f8(const tdg::AttnArgs* a, int hd, hipStream_t st);
 
 // ---------------------------------------------------------------- decode.hip
 // -1: hd not 16 / 64 (decode_attn), beam outside [1, 8] or V outside
-// [1, 65536] (beam_topk, sample_token, ensemble_logprobs), M outside [1, 8]
-// (ensemble_logprobs); nothing launched
+// [1, 65536] (beam_topk, sample_token, ensemble_logprobs, score_tokens), M
+// outside [1, 8] (ensemble_logprobs, score_tokens); nothing launched
 int tdg_decode_attn(const tdg::DecodeAttnArgs* a, int hd, hipStream_t st);
 int tdg_beam_topk(const tdg::BeamTopkArgs* a, hipStream_t st);
 int tdg_sample_token(const tdg::SampleArgs* a, hipStream_t st);
 int tdg_ensemble_logprobs(const tdg::EnsembleArgs* a, hipStream_t st);
+int tdg_score_tokens(const tdg::ScoreArgs* a, hipStream_t st);
 
 // ---------------------------------------------------------------- norm.hip
 // ctr: device RNG step counter (or null); site: dropout site id; y8 / s8 /

@@ -74,4 +74,16 @@ struct EnsembleArgs {
   int M, R, V, ldo, No;
 };
 
+// Teacher-forced scoring: the same mixture as EnsembleArgs, of which only the
+// label's column and (optionally) the row's largest value are kept.
+struct ScoreArgs {
+  const uint16_t* x[ENSEMBLE_MAX];  // member m: bf16 [R, ldl[m]], the first V columns count
+  float logw[ENSEMBLE_MAX];         // log of the weights (> 0, sum 1)
+  int ldl[ENSEMBLE_MAX];
+  const void* labels;  // [R] int32, or int64 with lab64
+  float* tok_lp;       // [R] mix[r, labels[r]]; 0 on a pad_id row, -inf outside [0, V)
+  float* top_lp;       // [R] max_v mix[r, v]; 0 on a pad_id row; null = not wanted
+  int M, R, V, lab64, pad_id;
+};
+
 }  // namespace tdg

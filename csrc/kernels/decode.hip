@@ -1,6 +1,7 @@
 // Decoding kernels (gfx950): single-query attention over an indexed K/V cache
-// the beam-search selection step, the sampling step and the ensemble's
-// probability average. Used by infer/step.py, infer/beam.py and infer/sample.py.
+// the beam-search selection step, the sampling step, the ensemble's
+// probability average and teacher-forced scoring under it. Used by
+// infer/step.py, infer/beam.py, infer/sample.py and infer/score.py.
 //
 // decode_attn: M = 1 per (row, head), so there is no matrix to feed the MFMA
 // units: the kernel is a stream over the keys. One wave per (row, head), four
@@ -31,6 +32,15 @@
 // re-reads the rows (at most 8 x 128 KiB, from L2) and stores the log of the
 // weighted mean probability, 16 bytes at a time. The members' pointers ride
 // in the argument block: nothing to upload before a launch.
+//
+// score_tokens: the same stream without the V-wide store. Pass 1 is
+// ensemble_logprobs' own (one function, member_offsets); one thread then forms
+// the label's mixture value from M scalar loads. The row's largest mixture
+// value, where asked for, is max - lse for one member and for more a second
+// pass from L2 that keeps a per-thread max, reduced in a fixed order. The
+// label's column and every other go through one expression (mix_column), so
+// tok_lp >= top_lp is exact. A row whose label is pad_id leaves before its
+// first load.
 #include "tdg_api.h"
 #include "tdg_common.h"
 
@@ -497,16 +507,18 @@ __global__ __launch_bounds__(256) void sample_token_kernel(const SampleArgs a) {
   }
 }
 
-// ---------------------------------------------------------------- ensemble_logprobs
+// ---------------------------------------------------------------- ensemble_logprobs, score_tokens
+// Pass 1 of both kernels: per member the row's logsumexp over its finite
+// logits, an online (max, sum) pair per thread and member reduced over the
+// workgroup in a fixed order. gm[m]: the row's largest finite logit (-inf: none);
+// off[m] = log w_m - lse_m, -inf for a member without a finite logit in the
+// row. Ends past its last barrier: `red` is free again after one more.
 template <int M>
-__global__ __launch_bounds__(256) void ensemble_logprobs_kernel(const EnsembleArgs a) {
-  __shared__ float red[ENSEMBLE_MAX][4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = blockIdx.x, V = a.V;
-  const uint16_t* x[M];
-#pragma unroll
-  for (int m = 0; m < M; ++m) x[m] = a.x[m] + (long long)r * a.ldl[m];
-
-  // pass 1: per member the row's logsumexp over its finite logits
+__device__ __forceinline__ void member_offsets(const uint16_t* (&x)[M],
+                                               const float (&logw)[ENSEMBLE_MAX], int V,
+                                               float (&red)[ENSEMBLE_MAX][4], float (&gm)[M],
+                                               float (&off)[M]) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float mx[M], sum[M];
 #pragma unroll
   for (int m = 0; m < M; ++m) {
@@ -540,7 +552,6 @@ __global__ __launch_bounds__(256) void ensemble_logprobs_kernel(const EnsembleAr
     if (lane == 0) red[m][wave] = w;
   }
   __syncthreads();
-  float gm[M];
 #pragma unroll
   for (int m = 0; m < M; ++m) gm[m] = fmaxf(fmaxf(red[m][0], red[m][1]), fmaxf(red[m][2], red[m][3]));
   __syncthreads();
@@ -550,13 +561,38 @@ __global__ __launch_bounds__(256) void ensemble_logprobs_kernel(const EnsembleAr
     if (lane == 0) red[m][wave] = w;
   }
   __syncthreads();
-  // off[m] = log w_m - lse_m; -inf: member m has no finite logit in this row
-  float off[M];
 #pragma unroll
   for (int m = 0; m < M; ++m) {
     const float tot = (red[m][0] + red[m][1]) + (red[m][2] + red[m][3]);
-    off[m] = gm[m] > -INFINITY ? a.logw[m] - (gm[m] + logf(tot)) : -INFINITY;
+    off[m] = gm[m] > -INFINITY ? logw[m] - (gm[m] + logf(tot)) : -INFINITY;
   }
+}
+
+// One column of the mixture: log sum_m exp(am(m)), am(m) = x_m + off_m or -inf
+// for a logit of probability 0; -inf where every member has none.
+template <int M, class A>
+__device__ __forceinline__ float mix_column(A am) {
+  float top = am(0);
+#pragma unroll
+  for (int m = 1; m < M; ++m) top = fmaxf(top, am(m));
+  float s = 0.f;
+  if (top > -INFINITY) {
+#pragma unroll
+    for (int m = 0; m < M; ++m) s += __expf(am(m) - top);
+  }
+  return top > -INFINITY ? top + logf(s) : -INFINITY;
+}
+
+template <int M>
+__global__ __launch_bounds__(256) void ensemble_logprobs_kernel(const EnsembleArgs a) {
+  __shared__ float red[ENSEMBLE_MAX][4];
+  const int tid = threadIdx.x, r = blockIdx.x, V = a.V;
+  const uint16_t* x[M];
+#pragma unroll
+  for (int m = 0; m < M; ++m) x[m] = a.x[m] + (long long)r * a.ldl[m];
+
+  float gm[M], off[M];
+  member_offsets<M>(x, a.logw, V, red, gm, off);
 
   // pass 2: out = log sum_m exp(x_m + off_m); the columns [V, No) get -inf
   uint16_t* const orow = a.out + (long long)r * a.ldo;
@@ -571,17 +607,7 @@ __global__ __launch_bounds__(256) void ensemble_logprobs_kernel(const EnsembleAr
           am[m][i] = (c + i < V && am[m][i] > -INFINITY) ? am[m][i] + off[m] : -INFINITY;
       }
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        float top = am[0][i];
-#pragma unroll
-        for (int m = 1; m < M; ++m) top = fmaxf(top, am[m][i]);
-        float s = 0.f;
-        if (top > -INFINITY) {
-#pragma unroll
-          for (int m = 0; m < M; ++m) s += __expf(am[m][i] - top);
-        }
-        o[i] = top > -INFINITY ? top + logf(s) : -INFINITY;
-      }
+      for (int i = 0; i < 8; ++i) o[i] = mix_column<M>([&](int m) { return am[m][i]; });
     } else {
 #pragma unroll
       for (int i = 0; i < 8; ++i) o[i] = -INFINITY;
@@ -598,6 +624,73 @@ __global__ __launch_bounds__(256) void ensemble_logprobs_kernel(const EnsembleAr
 template <int M>
 static void launch_ensemble(const EnsembleArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(ensemble_logprobs_kernel<M>, dim3(a.R), dim3(256), 0, st, a);
+}
+
+template <int M>
+__global__ __launch_bounds__(256) void score_tokens_kernel(const ScoreArgs a) {
+  __shared__ float red[ENSEMBLE_MAX][4];
+  const int tid = threadIdx.x, r = blockIdx.x, V = a.V;
+  // every branch below is workgroup-uniform
+  const long long lab = a.lab64 ? static_cast<const long long*>(a.labels)[r]
+                                : static_cast<const int*>(a.labels)[r];
+  if (lab == a.pad_id) {  // an ignored row: no logit is read
+    if (tid == 0) {
+      a.tok_lp[r] = 0.f;
+      if (a.top_lp) a.top_lp[r] = 0.f;
+    }
+    return;
+  }
+  const uint16_t* x[M];
+#pragma unroll
+  for (int m = 0; m < M; ++m) x[m] = a.x[m] + (long long)r * a.ldl[m];
+
+  float gm[M], off[M];
+  member_offsets<M>(x, a.logw, V, red, gm, off);
+
+  if (tid == 0) {  // the label's column: M scalar loads
+    float t = -INFINITY;
+    if (lab >= 0 && lab < V) {
+      float am[M];
+#pragma unroll
+      for (int m = 0; m < M; ++m) {
+        const float f = __uint_as_float((uint32_t)x[m][lab] << 16);
+        am[m] = f > -INFINITY ? f + off[m] : -INFINITY;
+      }
+      t = mix_column<M>([&](int m) { return am[m]; });
+    }
+    a.tok_lp[r] = t;
+  }
+  if (a.top_lp == nullptr) return;
+  if constexpr (M == 1) {
+    // x + off grows with x: the largest column is the largest logit's
+    if (tid == 0) {
+      const float am = gm[0] > -INFINITY ? gm[0] + off[0] : -INFINITY;
+      a.top_lp[r] = mix_column<1>([&](int) { return am; });
+    }
+  } else {
+    // pass 2 (rows from L2): the largest mixture value, nothing stored
+    float best = -INFINITY;
+    for (int c = tid * 8; c < V; c += 2048) {
+      float am[M][8];
+#pragma unroll
+      for (int m = 0; m < M; ++m) {
+        unpack8(*reinterpret_cast<const uint4*>(x[m] + c), am[m]);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          am[m][i] = (c + i < V && am[m][i] > -INFINITY) ? am[m][i] + off[m] : -INFINITY;
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) best = fmaxf(best, mix_column<M>([&](int m) { return am[m][i]; }));
+    }
+    __syncthreads();  // member_offsets' last reads of red
+    best = block_max(best, red[0]);
+    if (tid == 0) a.top_lp[r] = best;
+  }
+}
+
+template <int M>
+static void launch_score(const ScoreArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(score_tokens_kernel<M>, dim3(a.R), dim3(256), 0, st, a);
 }
 
 }  // namespace tdg
@@ -679,6 +772,28 @@ int tdg_ensemble_logprobs(const tdg::EnsembleArgs* a, hipStream_t st) {
     case 6: tdg::launch_ensemble<6>(*a, st); break;
     case 7: tdg::launch_ensemble<7>(*a, st); break;
     default: tdg::launch_ensemble<8>(*a, st); break;
+  }
+  return 0;
+}
+
+// Teacher-forced scores under that mixture (tdg_decode.h ScoreArgs), a
+// workgroup per row: tok_lp[r] = mix[r, labels[r]] and, where wanted,
+// top_lp[r] = max_v mix[r, v], both f32 and never rounded; nothing V-wide is
+// stored. A row whose label is pad_id gets 0 for both without a logit read, a
+// label outside [0, V) tok_lp -inf, a row no member has a finite logit in
+// -inf for both. ldl % 8 == 0, 16-byte aligned rows.
+int tdg_score_tokens(const tdg::ScoreArgs* a, hipStream_t st) {
+  if (a->M < 1 || a->M > tdg::ENSEMBLE_MAX || a->V < 1 || a->V > 65536) return -1;
+  if (a->R <= 0) return 0;
+  switch (a->M) {
+    case 1: tdg::launch_score<1>(*a, st); break;
+    case 2: tdg::launch_score<2>(*a, st); break;
+    case 3: tdg::launch_score<3>(*a, st); break;
+    case 4: tdg::launch_score<4>(*a, st); break;
+    case 5: tdg::launch_score<5>(*a, st); break;
+    case 6: tdg::launch_score<6>(*a, st); break;
+    case 7: tdg::launch_score<7>(*a, st); break;
+    default: tdg::launch_score<8>(*a, st); break;
   }
   return 0;
 }

@@ -3,7 +3,11 @@
     python -m tensorflow_distributed_on_gke_amd train [--config FILE] [--set key=value ...] [--nproc N]
     python -m tensorflow_distributed_on_gke_amd test  --weights PREFIX [PREFIX ...] [--ensemble-weights W ...]
             [--ema] [--sentence TEXT ...] [--beam N]
-            [--sample N --temperature T --top-k K --top-p P --seed S] [--input FILE --output FILE [--batch N]]
+            [--sample N --temperature T --top-k K --top-p P --seed S]
+            [--input FILE --output FILE [--batch N] [--n-best]]
+    python -m tensorflow_distributed_on_gke_amd score --weights PREFIX [PREFIX ...] [--ensemble-weights W ...]
+            [--ema] --input FILE --output FILE [--batch N] [--tokens] [--accuracy]
+            [--rerank [--length-penalty A] [--mix L]]
     python -m tensorflow_distributed_on_gke_amd average --inputs PREFIX PREFIX ... --output PREFIX
     python -m tensorflow_distributed_on_gke_amd heartbeat --port 3479
 
@@ -24,7 +28,19 @@ averaged weights a run with `ema_decay` wrote next to the snapshot
 (`<weights>_ema`). Several --weights prefixes decode as an ensemble
 (infer/ensemble.py): one model per prefix, all built from the same settings,
 their next-token probabilities averaged with --ensemble-weights (default:
-equal) at every step; --ema then applies to every prefix.
+equal) at every step; --ema then applies to every prefix. With --beam N
+--n-best the file holds all N hypotheses per source, best first.
+`score` is teacher-forced scoring (infer/score.py): how probable the model, or
+the ensemble, finds each target of source<TAB>target[<TAB>...] lines (the
+output of `test --input` is such a file). It writes
+source<TAB>target<TAB>logprob<TAB>n_tok lines in input order (--tokens: a fifth
+field, the tokens' log-probs) and prints pairs, skipped pairs (a side longer
+than the model's max_len: logprob nan, n_tok 0), tokens, total log-prob and
+perplexity exp(-total / tokens); --accuracy adds the share of tokens that are
+the model's first choice. With --rerank it writes one line per run of lines
+with equal source: the one that maximises logprob / ((5 + n_tok) / 6) ** A +
+L * the third input field (A default 0.6, as `test`; L default 0), ties to the
+first, with that key as its third field.
 `average` is checkpoint averaging: the mean of several weight bundles (float64
 on the host) as one f32 bundle `test --weights` and `warm_start` load.
 """
@@ -80,7 +96,9 @@ def cmd_train(args) -> int:
     return 0
 
 
-def cmd_test(args) -> int:
+def _load_tester(args):
+    """The Tester of `test` and `score`: the settings' tokenizers and one model
+    per --weights prefix (several: an ensemble)."""
     import torch
 
     from tensorflow_distributed_on_gke_amd.checkpoint import bundle
@@ -111,28 +129,38 @@ def cmd_test(args) -> int:
             if args.ema:
                 prefix += bundle.EMA_SUFFIX
                 if not os.path.exists(prefix + ".index"):
-                    raise FileNotFoundError(f"test --ema: no averaged weights at {prefix} (written next to "
+                    raise FileNotFoundError(f"{args.cmd} --ema: no averaged weights at {prefix} (written next to "
                                             "a snapshot by a run with ema_decay > 0)")
             bundle.load_weights(model.store, prefix)
         models.append(model)
     if len(models) > 1:
         from tensorflow_distributed_on_gke_amd.infer.ensemble import Ensemble
 
-        tester = Tester(tok, Ensemble(models, args.ensemble_weights))
-    else:
-        tester = Tester(tok, models[0])
+        return Tester(tok, Ensemble(models, args.ensemble_weights))
+    return Tester(tok, models[0])
+
+
+def _flat(text: str) -> str:
+    """A field of a tab-separated output line."""
+    return text.replace("\t", " ").replace("\n", " ").replace("\r", " ")
+
+
+def cmd_test(args) -> int:
+    tester = _load_tester(args)
     mode = dict(beam=args.beam, alpha=args.length_penalty, sample=args.sample,
                 temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
+    if args.n_best:
+        mode["n_best"] = True
     if args.input:
-        # file mode: source<TAB>hypothesis<TAB>score, input order, `sample` lines per source
+        # file mode: source<TAB>hypothesis<TAB>score, input order, `sample` (or, with
+        # --n-best, `beam`) lines per source
         with open(args.input, encoding="utf-8") as f:
             lines = [line.rstrip("\n") for line in f]
-        flat = lambda t: t.replace("\t", " ").replace("\n", " ").replace("\r", " ")
         hyps = tester.translate_lines(lines, batch=args.batch, max_length=args.max_length, **mode)
         with open(args.output, "w", encoding="utf-8") as f:
             for s, hs in zip(lines, hyps):
                 for h, sc in hs:
-                    f.write(f"{flat(s)}\t{flat(h)}\t{sc:.6f}\n")
+                    f.write(f"{_flat(s)}\t{_flat(h)}\t{sc:.6f}\n")
         print(f"{len(lines)} lines -> {args.output}")
         return 0
     text, tokens, attn = tester(list(args.sentence), max_length=args.max_length, **mode)
@@ -140,6 +168,74 @@ def cmd_test(args) -> int:
         for h in (t if args.sample > 0 else [t]):
             print(f"{s!r} -> {h!r}")
     print("attention maps:", {k: tuple(v.shape) for k, v in attn.items()})
+    return 0
+
+
+def _read_pairs(path: str, with_prior: bool):
+    """The fields of `score`'s input lines, source<TAB>target[<TAB>...], and,
+    `with_prior`, the number in every line's third field (else None)."""
+    with open(path, encoding="utf-8") as f:
+        rows = [line.rstrip("\n").split("\t") for line in f]
+    for n, r in enumerate(rows):
+        if len(r) < 2:
+            raise ValueError(f"{path} line {n + 1}: expected source<TAB>target")
+    prior = None
+    if with_prior:
+        try:
+            prior = [float(r[2]) for r in rows]
+        except (IndexError, ValueError):
+            raise ValueError(f"--mix needs a number in the third field of every line of {path}")
+    return rows, prior
+
+
+def cmd_score(args) -> int:
+    import math
+
+    rows, prior = args.pairs
+    tester = _load_tester(args)
+    scored = tester.score_pairs([r[0] for r in rows], [r[1] for r in rows], batch=args.batch,
+                                want_top=args.accuracy)
+    pairs = skipped = tokens = hits = 0
+    total = 0.0
+    out_lines = []
+    for r, (lp, n, tok_lp, top_lp) in zip(rows, scored):
+        pairs += 1
+        if n == 0 and lp != lp:
+            skipped += 1
+        else:
+            tokens += n
+            total += lp
+            if top_lp is not None:
+                hits += sum(1 for a, b in zip(tok_lp, top_lp) if a >= b)
+        line = f"{_flat(r[0])}\t{_flat(r[1])}\t{lp:.6f}\t{n}"
+        if args.tokens:
+            line += "\t" + " ".join(f"{x:.6f}" for x in tok_lp)
+        out_lines.append(line)
+    if args.rerank:
+        # a group: a maximal run of lines with one source; its best line, the first of equal keys
+        best = []
+        for i, (r, (lp, n, _, _)) in enumerate(zip(rows, scored)):
+            if lp != lp:
+                key = None  # not scored: never wins
+            else:
+                key = lp / ((5.0 + n) / 6.0) ** args.length_penalty
+                if prior is not None:
+                    key += args.mix * prior[i]
+            if i == 0 or r[0] != rows[i - 1][0]:
+                best.append((i, key))
+            elif key is not None and (best[-1][1] is None or key > best[-1][1]):
+                best[-1] = (i, key)
+        out_lines = [f"{_flat(rows[i][0])}\t{_flat(rows[i][1])}\t"
+                     + (f"{key:.6f}" if key is not None else "nan") for i, key in best]
+    with open(args.output, "w", encoding="utf-8") as f:
+        for line in out_lines:
+            f.write(line + "\n")
+    ppl = math.exp(-total / tokens) if tokens else float("nan")
+    msg = (f"{pairs} pairs ({skipped} skipped), {tokens} tokens, log-prob {total:.6f}, "
+           f"perplexity {ppl:.6f}")
+    if args.accuracy:
+        msg += f", accuracy {hits / tokens if tokens else float('nan'):.6f}"
+    print(msg + f" -> {args.output}")
     return 0
 
 
@@ -174,13 +270,14 @@ def main(argv=None) -> int:
     t.add_argument("--namespace", default=os.environ.get("POD_NAMESPACE", "default"))
     t.add_argument("--heartbeat-port", type=int, default=3479)
     t.add_argument("--master-port", type=int, default=int(os.environ.get("MASTER_PORT", 3480)))
-    e = sub.add_parser("test", parents=[common])
-    e.add_argument("--weights", nargs="+", default=None, metavar="PREFIX",
-                   help="weights prefix or directory; several (at most 8) decode as an ensemble")
-    e.add_argument("--ensemble-weights", nargs="+", type=float, default=None, metavar="W",
-                   help="one positive mixture weight per --weights prefix (default: equal)")
-    e.add_argument("--ema", action="store_true",
-                   help="load the averaged weights saved next to --weights (<prefix>_ema)")
+    models = argparse.ArgumentParser(add_help=False)
+    models.add_argument("--weights", nargs="+", default=None, metavar="PREFIX",
+                        help="weights prefix or directory; several (at most 8) are an ensemble")
+    models.add_argument("--ensemble-weights", nargs="+", type=float, default=None, metavar="W",
+                        help="one positive mixture weight per --weights prefix (default: equal)")
+    models.add_argument("--ema", action="store_true",
+                        help="load the averaged weights saved next to --weights (<prefix>_ema)")
+    e = sub.add_parser("test", parents=[common, models])
     e.add_argument("--sentence", action="append", default=None)
     e.add_argument("--max-length", type=int, default=20)
     e.add_argument("--beam", type=int, default=1, help="beam width (1 = greedy, at most 8)")
@@ -196,6 +293,22 @@ def main(argv=None) -> int:
     e.add_argument("--output", default=None, metavar="FILE",
                    help="source<TAB>hypothesis<TAB>score lines, in input order")
     e.add_argument("--batch", type=int, default=32, help="sentences per batch of --input")
+    e.add_argument("--n-best", action="store_true",
+                   help="with --beam N and --input: all N hypotheses per source, best first")
+    sc = sub.add_parser("score", parents=[common, models])
+    sc.add_argument("--input", default=None, metavar="FILE",
+                    help="source<TAB>target[<TAB>...] lines (the output of test --input is one)")
+    sc.add_argument("--output", default=None, metavar="FILE",
+                    help="source<TAB>target<TAB>logprob<TAB>n_tok lines, in input order")
+    sc.add_argument("--batch", type=int, default=32, help="pairs per batch")
+    sc.add_argument("--tokens", action="store_true", help="a fifth field: the tokens' log-probs")
+    sc.add_argument("--accuracy", action="store_true",
+                    help="also report the share of tokens that are the model's first choice")
+    sc.add_argument("--rerank", action="store_true",
+                    help="one line per run of equal sources: the best by logprob / "
+                         "((5 + n_tok) / 6) ** A + L * third input field, that key third")
+    sc.add_argument("--length-penalty", type=float, default=0.6, metavar="A")
+    sc.add_argument("--mix", type=float, default=0.0, metavar="L")
     a = sub.add_parser("average")
     a.add_argument("--inputs", nargs="+", required=True, metavar="PREFIX",
                    help="weight bundles (prefixes or snapshot directories) of one model")
@@ -203,25 +316,39 @@ def main(argv=None) -> int:
     h = sub.add_parser("heartbeat")
     h.add_argument("--port", type=int, default=3479)
     args = ap.parse_args(argv)
-    if args.cmd == "test":
+    if args.cmd in ("test", "score"):
         if args.ema and not args.weights:
-            ap.error("test: --ema needs --weights")
+            ap.error(f"{args.cmd}: --ema needs --weights")
         if args.weights and len(args.weights) > 8:
-            ap.error("test: an ensemble has at most 8 members")
+            ap.error(f"{args.cmd}: an ensemble has at most 8 members")
         if args.ensemble_weights is not None:
             if len(args.ensemble_weights) != len(args.weights or []):
-                ap.error("test: --ensemble-weights needs one value per --weights prefix")
+                ap.error(f"{args.cmd}: --ensemble-weights needs one value per --weights prefix")
             if not all(0.0 < w < float("inf") for w in args.ensemble_weights):
-                ap.error("test: --ensemble-weights must be finite and > 0")
+                ap.error(f"{args.cmd}: --ensemble-weights must be finite and > 0")
+    if args.cmd == "score":
+        if args.input is None or args.output is None:
+            ap.error("score: --input and --output are both needed")
+        if args.batch < 1:
+            ap.error("score: --batch must be at least 1")
+        if not args.rerank and (args.mix != 0.0 or args.length_penalty != 0.6):
+            ap.error("score: --mix and --length-penalty belong to --rerank")
+        try:  # before any model is built
+            args.pairs = _read_pairs(args.input, args.mix != 0.0)
+        except (OSError, ValueError) as e:
+            ap.error(f"score: {e}")
+    if args.cmd == "test":
         if (args.input is None) != (args.output is None) or (args.input and args.sentence):
             ap.error("test: --input and --output go together, without --sentence")
         if args.beam > 1 and args.sample > 0:
             ap.error("test: --beam and --sample exclude each other")
         if args.batch < 1 or args.sample < 0:
             ap.error("test: --batch must be at least 1 and --sample at least 0")
+        if args.n_best and (args.beam <= 1 or not args.input):
+            ap.error("test: --n-best lists the hypotheses of --beam N > 1 in file mode (--input)")
     if args.cmd == "test" and not args.sentence and not args.input:
         args.sentence = ["muitas pessoas vieram à estação."]  # reference test.py:9
-    return {"train": cmd_train, "test": cmd_test, "average": cmd_average,
+    return {"train": cmd_train, "test": cmd_test, "score": cmd_score, "average": cmd_average,
             "heartbeat": cmd_heartbeat}[args.cmd](args)
 
 

@@ -113,18 +113,22 @@ class Tester:
 
     def decode(self, src: torch.Tensor, max_length: int = 20, kv_cache: bool = True, beam: int = 1,
                alpha: float = 0.6, sample: int = 0, temperature: float = 1.0, top_k: int = 0,
-               top_p: float = 1.0, seed: int = 0, row_id0: int = 0
+               top_p: float = 1.0, seed: int = 0, row_id0: int = 0, n_best: bool = False
                ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """src int64 [B, S] -> (tokens int64 [B, n, 1 + len] on the CPU, scores
         f32 [B, n] or None): greedy (n = 1, no scores), beam search (beam > 1:
-        n = 1, the best hypothesis) or `sample` draws per sentence. An
-        ensemble decodes on the K/V cache only (`kv_cache=False` is an error),
-        and its greedy mode is beam search of width 1 with alpha 0, whose
-        score is returned."""
+        n = 1, the best hypothesis; with `n_best` n = beam, all of them by
+        descending ranking score, of which the first is that best one; a slot
+        that never held a hypothesis has score -inf) or `sample` draws per
+        sentence. An ensemble decodes on the K/V cache only (`kv_cache=False`
+        is an error), and its greedy mode is beam search of width 1 with
+        alpha 0, whose score is returned."""
         if sample < 0:
             raise ValueError(f"sample must be >= 0, got {sample}")
         if sample > 0 and beam > 1:
             raise ValueError("beam > 1 and sample > 0 exclude each other")
+        if n_best and beam <= 1:
+            raise ValueError("n_best lists the hypotheses of a beam search: it needs beam > 1")
         start, end = self.tgt_tok.start_end()
         ensemble = isinstance(self.model, Ensemble)
         if ensemble and not kv_cache:
@@ -137,10 +141,20 @@ class Tester:
                                            seed=seed, row_id0=row_id0)
             return tokens.cpu(), scores.cpu()
         if beam > 1 or ensemble:
-            from tensorflow_distributed_on_gke_amd.infer.beam import beam_search
+            from tensorflow_distributed_on_gke_amd.infer.beam import beam_search, length_penalty
 
-            tokens, scores = beam_search(self.model, src, start, end, beam=beam, max_length=max_length,
-                                         alpha=alpha if beam > 1 else 0.0)[:2]
+            tokens, scores, all_tokens, all_scores = beam_search(
+                self.model, src, start, end, beam=beam, max_length=max_length,
+                alpha=alpha if beam > 1 else 0.0)
+            if n_best:
+                # beam_search's own ranking: score / ((5 + len) / 6) ** alpha, len up to
+                # and including [END], the first of equal values first
+                is_end = (all_tokens[:, :, 1:] == end).long()
+                length = (is_end.cumsum(dim=2) - is_end == 0).sum(dim=2)
+                ranked = all_scores / length_penalty(length, alpha)
+                order = torch.sort(-ranked, dim=1, stable=True).indices
+                all_tokens = all_tokens.gather(1, order.unsqueeze(-1).expand_as(all_tokens))
+                return all_tokens.cpu(), all_scores.gather(1, order).cpu()
             return tokens.cpu().unsqueeze(1), scores.cpu().unsqueeze(1)
         out = (self.greedy_cached if kv_cache else self.greedy)(src, max_length).cpu()
         return out.unsqueeze(1), None
@@ -164,7 +178,9 @@ class Tester:
     def translate_lines(self, lines: Sequence[str], batch: int = 32, max_length: int = 20, **mode
                         ) -> List[List[Tuple[str, float]]]:
         """Per line, in input order, its (hypothesis, score) list: one entry
-        (greedy, beam) or `sample` entries. Lines are decoded `batch` at a
+        (greedy, beam), `beam` entries (beam search with `n_best`, best first;
+        slots that never held a hypothesis are left out) or `sample` entries.
+        Lines are decoded `batch` at a
         time in order of source length, so that a batch pads little; `mode`
         are the decoding arguments of `decode`. In sample mode line i's rows
         have the identities i * sample .. in the random stream, whichever
@@ -182,7 +198,47 @@ class Tester:
                 scores = self.score(src, tokens[:, 0]).view(-1, 1)
             for j, i in enumerate(idx):
                 out[i] = [(self._text(row)[0], float(scores[j, k]))
-                          for k, row in enumerate(tokens[j].tolist())]
+                          for k, row in enumerate(tokens[j].tolist())
+                          if not mode.get("n_best") or scores[j, k] > float("-inf")]
+        return out
+
+    def score_pairs(self, sources: Sequence[str], targets: Sequence[str], batch: int = 32,
+                    want_top: bool = False) -> List[Tuple[float, int, List[float], Optional[List[float]]]]:
+        """Per (source, target) pair of text, in input order, its teacher-forced
+        (log-probability, scored tokens, per-token log-probabilities,
+        per-token largest log-probabilities or None): infer/score.py on
+        targets tokenised as training tokenises them ([START] ... [END]). Pairs
+        are scored `batch` at a time in order of (source length, target
+        length), so that a batch pads little. A pair with a side longer than
+        the model's positional table is not scored: (nan, 0, [], None)."""
+        from tensorflow_distributed_on_gke_amd.infer.score import score_pairs
+
+        if len(sources) != len(targets):
+            raise ValueError(f"{len(sources)} sources for {len(targets)} targets")
+        src_rows = [self.src_tok.tokenize(s)[0] for s in sources]
+        tgt_rows = [self.tgt_tok.tokenize(t)[0] for t in targets]
+        slen = [int((r != PAD_ID).sum()) for r in src_rows]
+        tlen = [int((r != PAD_ID).sum()) for r in tgt_rows]
+        cfg = self.model.cfg
+        out: list = [(float("nan"), 0, [], None)] * len(sources)
+        order = sorted((i for i in range(len(sources))
+                        if slen[i] <= cfg.max_src_len and tlen[i] - 1 <= cfg.max_tgt_len),
+                       key=lambda i: (slen[i], tlen[i], i))
+        _, end = self.tgt_tok.start_end()
+        for b0 in range(0, len(order), batch):
+            idx = order[b0:b0 + batch]
+            src = torch.zeros(len(idx), max(slen[i] for i in idx), dtype=torch.int64)
+            tgt = torch.zeros(len(idx), max(tlen[i] for i in idx), dtype=torch.int64)
+            for j, i in enumerate(idx):
+                src[j, :slen[i]] = src_rows[i][:slen[i]]
+                tgt[j, :tlen[i]] = tgt_rows[i][:tlen[i]]
+            sc = score_pairs(self.model, src, tgt, want_top=want_top, end=end)
+            tok_lp, top_lp = sc.tok_lp.cpu(), sc.top_lp.cpu() if want_top else None
+            sent, n_tok = sc.sent_lp.cpu(), sc.n_tok.cpu()
+            for j, i in enumerate(idx):
+                n = int(n_tok[j])
+                out[i] = (float(sent[j]), n, tok_lp[j, :n].tolist(),
+                          top_lp[j, :n].tolist() if want_top else None)
         return out
 
     def _text(self, row: List[int]):

@@ -12,6 +12,10 @@ not re-exported: a name rebound here would not be seen by the module that
 reads it, so they are set on their owning module (the timed tile search's
 AUTOTUNE on `ops.tuning`). `gemm` and `workspace` name the functions here; the
 modules of those names are reached with `importlib.import_module`.
+
+The re-exported surface is the one the single-file module had and
+tests/test_kernels_surface_cpu.py pins; a wrapper added since is imported from
+its family module (`from ...ops.kernels.decode import score_tokens`).
 """
 from .workspace import NUM_CU, reset_workspace, workspace
 from .gemm import (EPI_BIAS, EPI_BIAS_RELU, EPI_DRELU, EPI_NONE, RAGGED_MAX_PROBLEMS,

@@ -1,5 +1,6 @@
 """Decoding steps (csrc/kernels/decode.hip): single-query attention, beam
-selection, sampling, the ensemble mixture -- each GPU arm with its CPU arm."""
+selection, sampling, the ensemble mixture and teacher-forced scoring under it
+-- each GPU arm with its CPU arm."""
 from __future__ import annotations
 
 import math
@@ -240,3 +241,56 @@ def ensemble_logprobs(logits_list, V: int, weights=None, out=None):
     out[:, :V] = mix
     out[:, V:] = ninf
     return out
+
+
+def score_tokens(logits_list, V: int, labels, weights=None, pad_id: int = 0, want_top: bool = False):
+    """Teacher-forced scores of one label per row under the mixture of
+    `ensemble_logprobs`, without the [R, V] mixture ever being stored.
+
+    logits_list, V, weights: as `ensemble_logprobs`; labels: int32 or int64
+    [R]. With mix = the mixture defined there, tok_lp[r] = mix[r, labels[r]]
+    (-inf for a label outside [0, V) or a column of probability 0) and
+    top_lp[r] = max_v mix[r, v]; a row whose label is pad_id is ignored: both
+    are 0 and its logits are not read. Returns (tok_lp f32 [R], top_lp f32 [R]
+    or None without `want_top`). The label's column goes through the same
+    arithmetic as every other, so tok_lp >= top_lp says exactly whether the
+    label is a most probable token. GPU: bf16 members as for
+    `ensemble_logprobs`, f32 arithmetic and outputs (csrc/kernels/decode.hip
+    score_tokens); CPU: the same definition in f32."""
+    M = len(logits_list)
+    if not 1 <= M <= ENSEMBLE_MAX:
+        raise RuntimeError(f"score_tokens: {M} members outside [1, {ENSEMBLE_MAX}]")
+    if not 1 <= V <= 65536:
+        raise RuntimeError(f"score_tokens: V {V} outside [1, 65536]")
+    w = [1.0] * M if weights is None else [float(x) for x in weights]
+    if len(w) != M or not all(0.0 < x < float("inf") for x in w):
+        raise RuntimeError(f"score_tokens: needs {M} finite weights > 0, got {w}")
+    total = math.fsum(w)
+    w = [x / total for x in w]
+    first = logits_list[0]
+    R = first.shape[0]
+    if labels.dim() != 1 or labels.numel() != R or labels.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError(f"score_tokens: labels must be int32 or int64 [{R}], got {labels.dtype} "
+                           f"{tuple(labels.shape)}")
+    if first.is_cuda:
+        tok_lp = torch.empty(R, dtype=torch.float32, device=first.device)
+        top_lp = torch.empty(R, dtype=torch.float32, device=first.device) if want_top else None
+        C().score_tokens(list(logits_list), V, w, labels, pad_id, tok_lp, top_lp)
+        return tok_lp, top_lp
+    ninf = float("-inf")
+    rows = []
+    for x, wm in zip(logits_list, w):
+        x = x[:, :V].float()
+        x = torch.where(x > ninf, x, torch.full_like(x, ninf))  # NaN too
+        lse = torch.logsumexp(x, dim=1, keepdim=True)
+        rows.append(torch.where(lse > ninf, x - lse + math.log(wm), torch.full_like(x, ninf)))
+    mix = torch.logsumexp(torch.stack(rows), dim=0)
+    lab = labels.long()
+    ignored = lab == pad_id
+    inside = (lab >= 0) & (lab < V)
+    zero = torch.zeros(R, dtype=torch.float32)
+    tok_lp = mix.gather(1, lab.clamp(0, V - 1).view(R, 1)).view(R)
+    tok_lp = torch.where(inside, tok_lp, torch.full_like(tok_lp, ninf))
+    tok_lp = torch.where(ignored, zero, tok_lp)
+    top_lp = torch.where(ignored, zero, mix.max(dim=1).values) if want_top else None
+    return tok_lp, top_lp
