@@ -21,6 +21,7 @@ using c10::optional;
 void def_gemm(py::module_& m);
 void def_attention(py::module_& m);
 void def_decode(py::module_& m);
+void def_overlap(py::module_& m);
 void def_layernorm(py::module_& m);
 void def_embedding(py::module_& m);
 void def_batch(py::module_& m);

@@ -6,6 +6,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   def_gemm(m);
   def_attention(m);
   def_decode(m);
+  def_overlap(m);
   def_layernorm(m);
   def_embedding(m);
   def_batch(m);

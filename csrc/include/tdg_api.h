@@ -12,6 +12,7 @@
 #include "tdg_attn.h"
 #include "tdg_decode.h"
 #include "tdg_distill.h"
+#include "tdg_overlap.h"
 
 extern "C" {
 
@@ -60,6 +61,11 @@ int tdg_beam_topk(const tdg::BeamTopkArgs* a, hipStream_t st);
 int tdg_sample_token(const tdg::SampleArgs* a, hipStream_t st);
 int tdg_ensemble_logprobs(const tdg::EnsembleArgs* a, hipStream_t st);
 int tdg_score_tokens(const tdg::ScoreArgs* a, hipStream_t st);
+
+// --------------------------------------------------------------- overlap.hip
+// -1: L outside [1, 512], N or P negative, ld < L; -2: a null operand; nothing
+// launched
+int tdg_ngram_matches(const tdg::NgramArgs* a, hipStream_t st);
 
 // ---------------------------------------------------------------- norm.hip
 // ctr: device RNG step counter (or null); site: dropout site id; y8 / s8 /

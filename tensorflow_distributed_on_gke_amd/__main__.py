@@ -3,11 +3,13 @@
     python -m tensorflow_distributed_on_gke_amd train [--config FILE] [--set key=value ...] [--nproc N]
     python -m tensorflow_distributed_on_gke_amd test  --weights PREFIX [PREFIX ...] [--ensemble-weights W ...]
             [--ema] [--sentence TEXT ...] [--beam N]
-            [--sample N --temperature T --top-k K --top-p P --seed S]
+            [--sample N --temperature T --top-k K --top-p P --seed S] [--mbr]
             [--input FILE --output FILE [--batch N] [--n-best]]
     python -m tensorflow_distributed_on_gke_amd score --weights PREFIX [PREFIX ...] [--ensemble-weights W ...]
             [--ema] --input FILE --output FILE [--batch N] [--tokens] [--accuracy]
             [--rerank [--length-penalty A] [--mix L]]
+    python -m tensorflow_distributed_on_gke_amd mbr   --input FILE --output FILE [--lc]
+    python -m tensorflow_distributed_on_gke_amd bleu  --hyp FILE --ref FILE [--hyp-field K] [--ref-field K] [--lc]
     python -m tensorflow_distributed_on_gke_amd average --inputs PREFIX PREFIX ... --output PREFIX
     python -m tensorflow_distributed_on_gke_amd heartbeat --port 3479
 
@@ -29,7 +31,12 @@ averaged weights a run with `ema_decay` wrote next to the snapshot
 (infer/ensemble.py): one model per prefix, all built from the same settings,
 their next-token probabilities averaged with --ensemble-weights (default:
 equal) at every step; --ema then applies to every prefix. With --beam N
---n-best the file holds all N hypotheses per source, best first.
+--n-best the file holds all N hypotheses per source, best first. With --mbr
+(and --sample N or --beam N, N >= 2, not with --n-best) one hypothesis per
+source is kept by minimum-Bayes-risk selection (infer/mbr.py): of the N
+candidates the one with the highest mean smoothed sentence BLEU against all of
+them; the file then holds source<TAB>hypothesis<TAB>model score<TAB>expected
+utility lines.
 `score` is teacher-forced scoring (infer/score.py): how probable the model, or
 the ensemble, finds each target of source<TAB>target[<TAB>...] lines (the
 output of `test --input` is such a file). It writes
@@ -41,6 +48,17 @@ the model's first choice. With --rerank it writes one line per run of lines
 with equal source: the one that maximises logprob / ((5 + n_tok) / 6) ** A +
 L * the third input field (A default 0.6, as `test`; L default 0), ties to the
 first, with that key as its third field.
+`mbr` is the same selection on text, without a model: of every run of
+source<TAB>candidate[<TAB>...] lines with equal source it writes
+source<TAB>best candidate<TAB>expected utility, ties to the first; the units are
+the candidates' whitespace-separated words (--lc: lowercased first).
+`bleu` is corpus BLEU (infer/bleu.py) of --hyp against --ref, one reference
+per line, over whitespace-separated words AS GIVEN: no tokenisation or
+detokenisation is applied (a "tokenize none" BLEU; tokenise both files
+beforehand to compare with other tools). --hyp-field / --ref-field K take the
+K-th tab-separated column (1-based; default: the whole line), so `--hyp out.tsv
+--hyp-field 2` reads the output of `test --input`. It prints one line: BLEU, the
+four n-gram precisions, brevity penalty, length ratio and both lengths.
 `average` is checkpoint averaging: the mean of several weight bundles (float64
 on the host) as one f32 bundle `test --weights` and `warm_start` load.
 """
@@ -151,21 +169,24 @@ def cmd_test(args) -> int:
                 temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
     if args.n_best:
         mode["n_best"] = True
+    if args.mbr:
+        mode["mbr"] = True
     if args.input:
         # file mode: source<TAB>hypothesis<TAB>score, input order, `sample` (or, with
-        # --n-best, `beam`) lines per source
+        # --n-best, `beam`) lines per source; --mbr: one, with its expected utility
         with open(args.input, encoding="utf-8") as f:
             lines = [line.rstrip("\n") for line in f]
         hyps = tester.translate_lines(lines, batch=args.batch, max_length=args.max_length, **mode)
         with open(args.output, "w", encoding="utf-8") as f:
             for s, hs in zip(lines, hyps):
-                for h, sc in hs:
-                    f.write(f"{_flat(s)}\t{_flat(h)}\t{sc:.6f}\n")
+                for h, sc, *utility in hs:
+                    f.write(f"{_flat(s)}\t{_flat(h)}\t{sc:.6f}" + "".join(f"\t{u:.6f}" for u in utility)
+                            + "\n")
         print(f"{len(lines)} lines -> {args.output}")
         return 0
     text, tokens, attn = tester(list(args.sentence), max_length=args.max_length, **mode)
     for s, t in zip(args.sentence, text):
-        for h in (t if args.sample > 0 else [t]):
+        for h in (t if args.sample > 0 and not args.mbr else [t]):
             print(f"{s!r} -> {h!r}")
     print("attention maps:", {k: tuple(v.shape) for k, v in attn.items()})
     return 0
@@ -239,6 +260,71 @@ def cmd_score(args) -> int:
     return 0
 
 
+def _device(name: str) -> str:
+    import torch
+
+    return name if name != "auto" else ("cuda:0" if torch.cuda.is_available() else "cpu")
+
+
+def _read_candidates(path: str):
+    """`mbr`'s input, source<TAB>candidate[<TAB>...] lines -> (sources,
+    candidate lists), one entry per maximal run of lines with equal source."""
+    sources, groups = [], []
+    with open(path, encoding="utf-8") as f:
+        for n, line in enumerate(f):
+            r = line.rstrip("\n").split("\t")
+            if len(r) < 2:
+                raise ValueError(f"{path} line {n + 1}: expected source<TAB>candidate")
+            if not sources or r[0] != sources[-1]:
+                sources.append(r[0])
+                groups.append([])
+            groups[-1].append(r[1])
+    return sources, groups
+
+
+def cmd_mbr(args) -> int:
+    from tensorflow_distributed_on_gke_amd.infer.mbr import select_text
+
+    sources, groups = args.groups
+    try:
+        picked = select_text(groups, lowercase=args.lc, device=_device(args.device))
+    except ValueError as e:
+        print(f"mbr: {args.input}: {e}", file=sys.stderr)
+        return 2
+    with open(args.output, "w", encoding="utf-8") as f:
+        for s, cands, (best, utility) in zip(sources, groups, picked):
+            f.write(f"{_flat(s)}\t{_flat(cands[best])}\t{utility:.6f}\n")
+    print(f"{len(groups)} groups, {sum(len(g) for g in groups)} candidates -> {args.output}")
+    return 0
+
+
+def _read_field(path: str, field: int):
+    """The lines of a file, or (field >= 1) their field-th tab-separated column."""
+    with open(path, encoding="utf-8") as f:
+        lines = [line.rstrip("\n") for line in f]
+    if field <= 0:
+        return lines
+    out = []
+    for n, line in enumerate(lines):
+        cols = line.split("\t")
+        if len(cols) < field:
+            raise ValueError(f"{path} line {n + 1}: no field {field}")
+        out.append(cols[field - 1])
+    return out
+
+
+def cmd_bleu(args) -> int:
+    from tensorflow_distributed_on_gke_amd.infer.bleu import corpus_bleu, format_bleu
+
+    try:
+        b = corpus_bleu(args.hyp_lines, args.ref_lines, lowercase=args.lc, device=_device(args.device))
+    except ValueError as e:
+        print(f"bleu: {e}", file=sys.stderr)
+        return 2
+    print(format_bleu(b))
+    return 0
+
+
 def cmd_average(args) -> int:
     from tensorflow_distributed_on_gke_amd.checkpoint import bundle
 
@@ -295,6 +381,9 @@ def main(argv=None) -> int:
     e.add_argument("--batch", type=int, default=32, help="sentences per batch of --input")
     e.add_argument("--n-best", action="store_true",
                    help="with --beam N and --input: all N hypotheses per source, best first")
+    e.add_argument("--mbr", action="store_true",
+                   help="with --sample N or --beam N (N >= 2): keep the candidate of highest expected "
+                        "utility; file mode adds that utility as a fourth field")
     sc = sub.add_parser("score", parents=[common, models])
     sc.add_argument("--input", default=None, metavar="FILE",
                     help="source<TAB>target[<TAB>...] lines (the output of test --input is one)")
@@ -309,6 +398,21 @@ def main(argv=None) -> int:
                          "((5 + n_tok) / 6) ** A + L * third input field, that key third")
     sc.add_argument("--length-penalty", type=float, default=0.6, metavar="A")
     sc.add_argument("--mix", type=float, default=0.0, metavar="L")
+    mb = sub.add_parser("mbr")
+    mb.add_argument("--input", required=True, metavar="FILE",
+                    help="source<TAB>candidate[<TAB>...] lines, a source's candidates on consecutive lines")
+    mb.add_argument("--output", required=True, metavar="FILE",
+                    help="source<TAB>best candidate<TAB>expected utility, one line per source")
+    mb.add_argument("--lc", action="store_true", help="lowercase the candidates first")
+    mb.add_argument("--device", default="auto")
+    bl = sub.add_parser("bleu")
+    bl.add_argument("--hyp", required=True, metavar="FILE")
+    bl.add_argument("--ref", required=True, metavar="FILE", help="one reference per hypothesis line")
+    bl.add_argument("--hyp-field", type=int, default=0, metavar="K",
+                    help="the K-th tab-separated column of --hyp (1-based; default: the whole line)")
+    bl.add_argument("--ref-field", type=int, default=0, metavar="K")
+    bl.add_argument("--lc", action="store_true", help="lowercase both sides first")
+    bl.add_argument("--device", default="auto")
     a = sub.add_parser("average")
     a.add_argument("--inputs", nargs="+", required=True, metavar="PREFIX",
                    help="weight bundles (prefixes or snapshot directories) of one model")
@@ -346,10 +450,30 @@ def main(argv=None) -> int:
             ap.error("test: --batch must be at least 1 and --sample at least 0")
         if args.n_best and (args.beam <= 1 or not args.input):
             ap.error("test: --n-best lists the hypotheses of --beam N > 1 in file mode (--input)")
+        if args.mbr and max(args.beam, args.sample) < 2:
+            ap.error("test: --mbr selects among candidates: it needs --sample N or --beam N, N >= 2")
+        if args.mbr and args.n_best:
+            ap.error("test: --mbr keeps one hypothesis per source: not with --n-best")
+    if args.cmd == "mbr":
+        try:  # before anything else runs
+            args.groups = _read_candidates(args.input)
+        except (OSError, ValueError) as e:
+            ap.error(f"mbr: {e}")
+    if args.cmd == "bleu":
+        if args.hyp_field < 0 or args.ref_field < 0:
+            ap.error("bleu: --hyp-field and --ref-field count columns from 1")
+        try:
+            args.hyp_lines = _read_field(args.hyp, args.hyp_field)
+            args.ref_lines = _read_field(args.ref, args.ref_field)
+        except (OSError, ValueError) as e:
+            ap.error(f"bleu: {e}")
+        if len(args.hyp_lines) != len(args.ref_lines):
+            ap.error(f"bleu: {args.hyp} has {len(args.hyp_lines)} lines, {args.ref} "
+                     f"{len(args.ref_lines)}")
     if args.cmd == "test" and not args.sentence and not args.input:
         args.sentence = ["muitas pessoas vieram à estação."]  # reference test.py:9
-    return {"train": cmd_train, "test": cmd_test, "score": cmd_score, "average": cmd_average,
-            "heartbeat": cmd_heartbeat}[args.cmd](args)
+    return {"train": cmd_train, "test": cmd_test, "score": cmd_score, "mbr": cmd_mbr, "bleu": cmd_bleu,
+            "average": cmd_average, "heartbeat": cmd_heartbeat}[args.cmd](args)
 
 
 if __name__ == "__main__":

@@ -113,8 +113,8 @@ class Tester:
 
     def decode(self, src: torch.Tensor, max_length: int = 20, kv_cache: bool = True, beam: int = 1,
                alpha: float = 0.6, sample: int = 0, temperature: float = 1.0, top_k: int = 0,
-               top_p: float = 1.0, seed: int = 0, row_id0: int = 0, n_best: bool = False
-               ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+               top_p: float = 1.0, seed: int = 0, row_id0: int = 0, n_best: bool = False,
+               mbr: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """src int64 [B, S] -> (tokens int64 [B, n, 1 + len] on the CPU, scores
         f32 [B, n] or None): greedy (n = 1, no scores), beam search (beam > 1:
         n = 1, the best hypothesis; with `n_best` n = beam, all of them by
@@ -122,7 +122,9 @@ class Tester:
         that never held a hypothesis has score -inf) or `sample` draws per
         sentence. An ensemble decodes on the K/V cache only (`kv_cache=False`
         is an error), and its greedy mode is beam search of width 1 with
-        alpha 0, whose score is returned."""
+        alpha 0, whose score is returned. `mbr`: of the `sample` draws, or of
+        the beam's hypotheses, the one of highest expected utility
+        (`decode_mbr`), in the n = 1 form, with its model score."""
         if sample < 0:
             raise ValueError(f"sample must be >= 0, got {sample}")
         if sample > 0 and beam > 1:
@@ -133,6 +135,12 @@ class Tester:
         ensemble = isinstance(self.model, Ensemble)
         if ensemble and not kv_cache:
             raise ValueError("an ensemble decodes with the K/V cache: kv_cache=False is not supported")
+        if mbr:
+            if n_best:
+                raise ValueError("mbr keeps one hypothesis per sentence: it does not go with n_best")
+            return self.decode_mbr(src, max_length, beam=beam, alpha=alpha, sample=sample,
+                                   temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                                   row_id0=row_id0)[:2]
         if sample > 0:
             from tensorflow_distributed_on_gke_amd.infer.sample import sample_search
 
@@ -159,6 +167,43 @@ class Tester:
         out = (self.greedy_cached if kv_cache else self.greedy)(src, max_length).cpu()
         return out.unsqueeze(1), None
 
+    def decode_mbr(self, src: torch.Tensor, max_length: int = 20, beam: int = 1, alpha: float = 0.6,
+                   sample: int = 0, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                   seed: int = 0, row_id0: int = 0
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Minimum-Bayes-risk decoding (infer/mbr.py): the candidates of a
+        sentence are its `sample` >= 2 draws, or the hypotheses of its beam
+        search of width `beam` >= 2 (slots of score -inf, which never held
+        one, left out), and the one closest to all of them is kept. Selection
+        runs on the device tokens, before anything is copied to the host.
+        src int64 [B, S] -> (tokens int64 [B, 1, 1 + len], the kept
+        candidate's model score f32 [B, 1], its expected utility f64 [B]), on
+        the CPU."""
+        from tensorflow_distributed_on_gke_amd.infer.mbr import mbr_select
+
+        if sample > 0 and beam > 1:
+            raise ValueError("beam > 1 and sample > 0 exclude each other")
+        if max(sample, beam) < 2:
+            raise ValueError("mbr selects among candidates: it needs sample >= 2 or beam >= 2")
+        start, end = self.tgt_tok.start_end()
+        valid = None
+        if sample > 0:
+            from tensorflow_distributed_on_gke_amd.infer.sample import sample_search
+
+            tokens, scores = sample_search(self.model, src, start, end, n=sample, max_length=max_length,
+                                           temperature=temperature, top_k=top_k, top_p=top_p,
+                                           seed=seed, row_id0=row_id0)
+        else:
+            from tensorflow_distributed_on_gke_amd.infer.beam import beam_search
+
+            _, _, tokens, scores = beam_search(self.model, src, start, end, beam=beam,
+                                               max_length=max_length, alpha=alpha)
+            valid = scores > float("-inf")
+        best, expected = mbr_select(tokens, end, PAD_ID, valid)
+        pick = best.view(-1, 1)
+        kept = tokens.gather(1, pick.unsqueeze(-1).expand(-1, 1, tokens.shape[2]))
+        return kept.cpu(), scores.gather(1, pick).cpu(), expected.gather(1, pick).view(-1).cpu()
+
     @torch.no_grad()
     def score(self, src: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
         """Teacher-forced f32 log-probability [B] of tokens int64 [B, 1 + len]
@@ -180,12 +225,17 @@ class Tester:
         """Per line, in input order, its (hypothesis, score) list: one entry
         (greedy, beam), `beam` entries (beam search with `n_best`, best first;
         slots that never held a hypothesis are left out) or `sample` entries.
-        Lines are decoded `batch` at a
+        With `mbr=True` (and sample >= 2 or beam >= 2) one entry, the
+        candidate `decode_mbr` keeps, as (hypothesis, score, expected
+        utility). Lines are decoded `batch` at a
         time in order of source length, so that a batch pads little; `mode`
         are the decoding arguments of `decode`. In sample mode line i's rows
         have the identities i * sample .. in the random stream, whichever
         batch the line falls into."""
         n = max(1, mode.get("sample", 0))
+        mbr = mode.get("mbr", False)
+        if mbr and mode.get("n_best"):
+            raise ValueError("mbr keeps one hypothesis per sentence: it does not go with n_best")
         lens = [int((self.src_tok.tokenize(s) != PAD_ID).sum()) for s in lines]
         order = sorted(range(len(lines)), key=lambda i: (lens[i], i))
         out: List[List[Tuple[str, float]]] = [[] for _ in lines]
@@ -193,6 +243,13 @@ class Tester:
             idx = order[b0:b0 + batch]
             src = self.src_tok.tokenize([lines[i] for i in idx])
             kw = dict(mode, row_id0=[i * n for i in idx]) if mode.get("sample", 0) > 0 else mode
+            if mbr:
+                kw = {k: v for k, v in kw.items() if k not in ("mbr", "kv_cache")}
+                tokens, scores, utility = self.decode_mbr(src, max_length, **kw)
+                for j, i in enumerate(idx):
+                    out[i] = [(self._text(tokens[j, 0].tolist())[0], float(scores[j, 0]),
+                               float(utility[j]))]
+                continue
             tokens, scores = self.decode(src, max_length, **kw)
             if scores is None:
                 scores = self.score(src, tokens[:, 0]).view(-1, 1)
@@ -251,22 +308,25 @@ class Tester:
 
     def __call__(self, sentence: Union[str, Sequence[str]], max_length: int = 20, kv_cache: bool = True,
                  beam: int = 1, alpha: float = 0.6, sample: int = 0, temperature: float = 1.0,
-                 top_k: int = 0, top_p: float = 1.0, seed: int = 0
+                 top_k: int = 0, top_p: float = 1.0, seed: int = 0, mbr: bool = False
                  ) -> Tuple[Union[str, List[str]], list, Dict[str, torch.Tensor]]:
         """beam > 1: beam search (infer/beam.py) with length penalty `alpha`
         instead of the greedy argmax; the return value has the same form.
         sample > 0: `sample` translations per sentence drawn with temperature,
         top-k and top-p (infer/sample.py); texts and tokens are then a list per
-        sentence, the attention maps those of every sentence's first sample."""
+        sentence, the attention maps those of every sentence's first sample.
+        mbr: of those samples, or of the beam's hypotheses, the one `decode_mbr`
+        keeps, in the form of the greedy result."""
         single = isinstance(sentence, str)
         src = self.src_tok.tokenize(sentence)
         out, _ = self.decode(src, max_length, kv_cache=kv_cache, beam=beam, alpha=alpha, sample=sample,
-                             temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+                             temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, mbr=mbr)
+        many = sample > 0 and not mbr
         texts, tokens = [], []
         for rows in out.tolist():
             pairs = [self._text(row) for row in rows]
-            texts.append([p[0] for p in pairs] if sample > 0 else pairs[0][0])
-            tokens.append([p[1] for p in pairs] if sample > 0 else pairs[0][1])
+            texts.append([p[0] for p in pairs] if many else pairs[0][0])
+            tokens.append([p[1] for p in pairs] if many else pairs[0][1])
         attn = self.attention_weights(src, out[:, 0, :-1])
         if single:
             return texts[0], tokens[0], attn
