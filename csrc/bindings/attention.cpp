@@ -440,6 +440,12 @@ void attn_probs(const Tensor& q, const Tensor& k, const Tensor& probs,
             "tdg attn_probs");
 }
 
+std::vector<int64_t> attn_last_plan() {
+  int p[5];
+  tdg_attn_last_plan(p);
+  return std::vector<int64_t>(p, p + 5);
+}
+
 }  // namespace
 
 void def_attention(py::module_& m) {
@@ -451,4 +457,5 @@ void def_attention(py::module_& m) {
   m.def("attn_bwd_g8", &attn_bwd_g8);
   m.def("attn_bwd_f8", &attn_bwd_f8);
   m.def("attn_probs", &attn_probs);
+  m.def("attn_last_plan", &attn_last_plan);
 }

@@ -51,6 +51,11 @@ int tdg_attn_bwd_fdo(const tdg::AttnArgs* a, hipStream_t st);
 int tdg_attn_probs(const tdg::AttnArgs* a, int hd, float* probs, hipStream_t st);
 int tdg_attn_fwd_fp8(const tdg::AttnArgs* a, int hd, hipStream_t st);
 int tdg_attn_bwd_f8(const tdg::AttnArgs* a, int hd, hipStream_t st);
+// The bf16 attention launch this thread made last, as its launcher recorded
+// it: kernel family (attn_impl.h AttnPlanFamily), head dim, workgroups and
+// threads per workgroup, workgroups of the backward's second (dK/dV) launch
+// or 0. family -1: none yet. The fp8 launchers do not record. Host only.
+void tdg_attn_last_plan(int out[5]);
 
 // ---------------------------------------------------------------- decode.hip
 // -1: hd not 16 / 64 (decode_attn), beam outside [1, 8] or V outside

@@ -1153,6 +1153,7 @@ extern "C" int tdg_attn_bwd_fdo(const AttnArgs* ap, hipStream_t st) {
     return -1;
   constexpr int lds = fused_bwd_lds<64>() > FDO_STAGES * FDO_SB ? fused_bwd_lds<64>() : FDO_STAGES * FDO_SB;
   big_lds<attn_bwd_fused_kernel<64, 1, true>>();
+  attn_plan_record(ATTN_BWD_FDO, 64, (long long)a.B * a.H, 512);
   hipLaunchKernelGGL((attn_bwd_fused_kernel<64, 1, true>), dim3(a.B * a.H), dim3(512), lds, st, a);
   return 0;
 }
@@ -1167,6 +1168,7 @@ int bwd_hd(const AttnArgs& a, hipStream_t st) {
     // call, step 5.15 vs 5.13 ms (profiles/r3s2/attn_bwd_u2.txt)
     constexpr int U = 1;
     big_lds<attn_bwd_fused_kernel<HD, U>>();
+    attn_plan_record(ATTN_BWD_FUSED, HD, (long long)a.B * a.H, 512 / U);
     hipLaunchKernelGGL((attn_bwd_fused_kernel<HD, U>), dim3(a.B * a.H), dim3(512 / U), lds, st, a);
     return 0;
   }
@@ -1179,12 +1181,16 @@ int bwd_hd(const AttnArgs& a, hipStream_t st) {
     constexpr int lds_kv = NS * (2 * ATile<64>::BYTES + 768);
     big_lds<attn_bwd_dq_pipe_kernel<U, NS>>();
     big_lds<attn_bwd_dkdv_pipe_kernel<U, NS>>();
+    attn_plan_record(ATTN_BWD_PIPE, HD, (long long)cdiv(a.Lq, 64 * U) * a.H * a.B, 256,
+                     (long long)cdiv(a.Lk, 64 * U) * a.H * a.B);
     hipLaunchKernelGGL((attn_bwd_dq_pipe_kernel<U, NS>), dim3(cdiv(a.Lq, 64 * U), a.H, a.B),
                        dim3(256), lds_dq, st, a);
     hipLaunchKernelGGL((attn_bwd_dkdv_pipe_kernel<U, NS>), dim3(cdiv(a.Lk, 64 * U), a.H, a.B),
                        dim3(256), lds_kv, st, a);
     return 0;
   }
+  attn_plan_record(ATTN_BWD_SPLIT, HD, (long long)cdiv(a.Lq, QB) * a.H * a.B, 256,
+                   (long long)cdiv(a.Lk, KB) * a.H * a.B);
   hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, 1>), dim3(cdiv(a.Lq, QB), a.H, a.B), dim3(256),
                      2 * ATile<HD>::BYTES, st, a);
   hipLaunchKernelGGL((attn_bwd_dkdv_kernel<HD, 1>), dim3(cdiv(a.Lk, KB), a.H, a.B), dim3(256),

@@ -310,6 +310,7 @@ int fwd_hd(const AttnArgs& a, hipStream_t st) {
     if (a.Lq > 128) {
       constexpr int NWV = 8, U = 1, NS = 3;
       big_lds<attn_fwd_pipe_kernel<NWV, U, NS>>();
+      attn_plan_record(ATTN_FWD_PIPE, HD, (long long)cdiv(a.Lq, 16 * NWV * U) * a.H * a.B, NWV * 64);
       hipLaunchKernelGGL((attn_fwd_pipe_kernel<NWV, U, NS>), dim3(cdiv(a.Lq, 16 * NWV * U), a.H, a.B),
                          dim3(NWV * 64), NS * 2 * ATile<64>::BYTES, st, a);
       return 0;
@@ -324,12 +325,15 @@ int fwd_hd(const AttnArgs& a, hipStream_t st) {
     // rounds (profiles/r3s2/attn_short_fwd_variants.txt); headline step
     // 5.04-5.06 vs 5.07-5.08 ms A/B (profiles/r3s2/attn_short_fwd_ab.txt)
     // (hd 128: 8 waves x 1 subtile, two subtiles per wave would spill)
+    attn_plan_record(HD <= 64 ? ATTN_FWD128 : ATTN_FWD128W8, HD, (long long)grid.x * grid.y * grid.z,
+                     HD <= 64 ? 256 : 512);
     if constexpr (HD <= 64)
       hipLaunchKernelGGL((attn_fwd_kernel<HD, 4, 128, 2>), grid, dim3(256), 4 * ATile<HD>::BYTES, st, a);
     else
       hipLaunchKernelGGL((attn_fwd_kernel<HD, 8, 128, 1>), grid, dim3(512), 4 * ATile<HD>::BYTES, st, a);
   } else {
     dim3 grid(cdiv(a.Lq, 64), a.H, a.B);
+    attn_plan_record(ATTN_FWD64, HD, (long long)grid.x * grid.y * grid.z, 256);
     hipLaunchKernelGGL((attn_fwd_kernel<HD, 4, 64, 1>), grid, dim3(256), 2 * ATile<HD>::BYTES, st, a);
   }
   return 0;
@@ -337,12 +341,18 @@ int fwd_hd(const AttnArgs& a, hipStream_t st) {
 template <int HD>
 int probs_hd(const AttnArgs& a, float* probs, hipStream_t st) {
   const long long rows = (long long)a.B * a.H * a.Lq;
+  attn_plan_record(ATTN_PROBS, HD, (rows + 3) / 4, 256);
   hipLaunchKernelGGL(attn_probs_kernel<HD>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a,
                      probs);
   return 0;
 }
 }  // namespace
 
+// (the record every bf16 attention launcher writes: attn_impl.h attn_plan_record)
+extern "C" void tdg_attn_last_plan(int out[5]) {
+  const int* p = attn_plan_slot();
+  for (int i = 0; i < 5; ++i) out[i] = p[i];
+}
 extern "C" int tdg_attn_fwd(const AttnArgs* a, int hd, hipStream_t st) {
   TDG_HD_CASES(fwd_hd, *a, st)
 }

@@ -434,6 +434,33 @@ __device__ __forceinline__ float row_delta(const short8_t (&of)[KS], const short
   return rows_sum(d);
 }
 
+// The launch about to be made, for tdg_attn_last_plan (tdg_api.h): kernel
+// family, head dim, workgroups and threads per workgroup of the (first)
+// launch, workgroups of the second launch (the split / pipelined backward's
+// dK/dV kernel; 0 otherwise). One thread-local record, written by the
+// launcher that launches: nothing here predicts a dispatch. Host only.
+enum AttnPlanFamily : int {
+  ATTN_FWD64 = 0,     // attn_fwd_kernel<HD, 4, 64, 1>
+  ATTN_FWD128 = 1,    // attn_fwd_kernel<HD, 4, 128, 2>
+  ATTN_FWD128W8 = 2,  // attn_fwd_kernel<128, 8, 128, 1>
+  ATTN_FWD_PIPE = 3,
+  ATTN_PROBS = 4,
+  ATTN_BWD_FUSED = 5,
+  ATTN_BWD_FDO = 6,
+  ATTN_BWD_SPLIT = 7,
+  ATTN_BWD_PIPE = 8,
+  ATTN_QKV_SELF = 9,
+  ATTN_QKV_CROSS = 10,
+};
+inline int* attn_plan_slot() {
+  static thread_local int plan[5] = {-1, 0, 0, 0, 0};
+  return plan;
+}
+inline void attn_plan_record(int family, int hd, long long wgs, int threads, long long wgs2 = 0) {
+  int* p = attn_plan_slot();
+  p[0] = family; p[1] = hd; p[2] = (int)wgs; p[3] = threads; p[4] = (int)wgs2;
+}
+
 }  // namespace tdg
 
 // (big_lds<Kernel>(): tdg_common.h)

@@ -283,6 +283,7 @@ template <int STAGES, bool CROSS, bool SB1>
 void qkv_attn_launch(const QkvAttnArgs& qa, hipStream_t st) {
   constexpr int SB = (128 + (CROSS ? 64 : 192)) * BK * 2;
   big_lds<qkv_attn_fwd_kernel<STAGES, CROSS, SB1>>();
+  attn_plan_record(CROSS ? ATTN_QKV_CROSS : ATTN_QKV_SELF, 64, (long long)qa.a.B * qa.a.H, 512);
   hipLaunchKernelGGL((qkv_attn_fwd_kernel<STAGES, CROSS, SB1>), dim3(qa.a.B * qa.a.H), dim3(512),
                      STAGES * SB, st, qa);
 }
