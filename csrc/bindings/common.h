@@ -9,6 +9,7 @@
 #include <c10/hip/HIPStream.h>
 #include <c10/core/DeviceGuard.h>
 
+#include <cmath>
 #include <vector>
 
 #include "tdg_api.h"
@@ -74,6 +75,43 @@ inline void check_extent(const Tensor& t, long long rows, long long ld, long lon
   TORCH_CHECK(need <= have, n, ": operand extent ", need, " exceeds storage ", have);
 }
 inline int64_t round8(int64_t v) { return (v + 7) / 8 * 8; }
+
+// The members of a mixture (tdg_decode.h MemberRows): bf16 tensors [R, >= V] on
+// `dev`, rows contiguous, each with its own row stride, and one number per
+// member: its weight, > 0 (the Python wrapper normalises them to sum 1), or,
+// with `logs`, the logarithm of that; the kernel gets the logarithms. vec: the
+// kernel loads 16 bytes at a time, so every row lies on a 16-byte boundary, the
+// strides are multiples of 8 and the columns up to round8(V) lie inside the
+// storage; without it any rows of V columns do. `op` and `what` name the call
+// and a member in the messages. Members past MEMBERS_MAX are checked but not
+// stored: the launcher refuses their count.
+inline void check_members(const std::vector<Tensor>& members, int64_t V, const std::vector<double>& w,
+                          bool logs, int64_t R, const c10::Device& dev, const char* op,
+                          const char* what, bool vec, tdg::MemberRows* out) {
+  TORCH_CHECK(w.size() == members.size(), op, ": ", w.size(), " weights for ", members.size(), " ",
+              what, " tensors");
+  for (size_t m = 0; m < members.size(); ++m) {
+    const Tensor& t = members[m];
+    check_bf16(t, what);
+    TORCH_CHECK(t.device() == dev, op, ": every ", what, " and the other operands on one device");
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == R && t.stride(1) == 1 && t.size(1) >= V, op, ": every ",
+                what, " must be [R, >= V], rows contiguous");
+    const int64_t ld = t.stride(0);
+    TORCH_CHECK(ld < (1LL << 31) && (R <= 1 || ld >= (vec ? round8(V) : t.size(1))) &&
+                    (!vec || ld % 8 == 0),
+                op, ": ", what, " row stride ", ld, vec ? " must be a multiple of 8" : " too small");
+    if (vec) check_aligned(t, 16, what);
+    check_extent(t, R, ld, vec ? round8(V) : V, what);
+    const double lw = logs ? w[m] : std::log(w[m]);
+    TORCH_CHECK(std::isfinite(w[m]) && (logs || w[m] > 0) && std::isfinite(lw), op,
+                ": weights must be finite and > 0, got ", logs ? std::exp(lw) : w[m]);
+    if (m < (size_t)tdg::MEMBERS_MAX) {
+      out->x[m] = static_cast<const uint16_t*>(t.data_ptr());
+      out->ld[m] = (int)(R > 1 ? ld : t.size(1));  // one row: its stride is never used
+      out->logw[m] = (float)lw;
+    }
+  }
+}
 
 // One fp8 amax slot (64 words, 32 apart), or null.
 inline unsigned* amax_ptr(const optional<Tensor>& t) {

@@ -195,39 +195,11 @@ void sample_token(const Tensor& logits, int64_t V, const Tensor& score, const Te
   check_err(tdg_sample_token(&a, stream_of(logits)), "tdg sample_token");
 }
 
-// The members of a mixture (EnsembleArgs / ScoreArgs): M bf16 tensors [R, >= V]
-// on `dev`, each with its own row stride, and their weights, > 0 (the Python
-// wrapper normalises them to sum 1); the kernel gets their logarithms.
-void check_members(const std::vector<Tensor>& logits, int64_t V, const std::vector<double>& weights,
-                   int64_t R, const c10::Device& dev, const char* op, const uint16_t** x, int* ldls,
-                   float* logw) {
-  const int64_t M = (int64_t)logits.size();
-  for (int64_t m = 0; m < M; ++m) {
-    const Tensor& t = logits[m];
-    check_bf16(t, "logits");
-    TORCH_CHECK(t.device() == dev, op, ": members and outputs on one device");
-    TORCH_CHECK(t.dim() == 2 && t.size(0) == R && t.stride(1) == 1 && t.size(1) >= V,
-                "every member's logits must be [R, >= V], rows contiguous");
-    const int64_t ldl = t.stride(0);
-    TORCH_CHECK(ldl < (1LL << 31) && ldl % 8 == 0 && (ldl >= round8(V) || R <= 1), op,
-                ": logits row stride must be a multiple of 8");
-    check_aligned(t, 16, "logits");
-    check_extent(t, R, ldl, round8(V), "logits");
-    TORCH_CHECK(std::isfinite(weights[m]) && weights[m] > 0 && std::isfinite(std::log(weights[m])),
-                op, ": weights must be finite and > 0, got ", weights[m]);
-    x[m] = (const uint16_t*)t.data_ptr();
-    ldls[m] = (int)ldl;
-    logw[m] = (float)std::log(weights[m]);
-  }
-}
-
 void ensemble_logprobs(const std::vector<Tensor>& logits, int64_t V,
                        const std::vector<double>& weights, const Tensor& out) {
   const int64_t M = (int64_t)logits.size();
   TORCH_CHECK(M >= 1 && M <= tdg::ENSEMBLE_MAX, "ensemble_logprobs: 1 to ", tdg::ENSEMBLE_MAX,
               " members, got ", M);
-  TORCH_CHECK((int64_t)weights.size() == M, "ensemble_logprobs: ", weights.size(), " weights for ",
-              M, " members");
   TORCH_CHECK(V >= 1 && V <= 65536, "ensemble_logprobs: V must be in [1, 65536], got ", V);
   check_bf16(out, "out");
   TORCH_CHECK(out.dim() == 2 && out.stride(1) == 1 && out.size(1) >= V && out.size(1) % 8 == 0,
@@ -239,7 +211,7 @@ void ensemble_logprobs(const std::vector<Tensor>& logits, int64_t V,
   check_aligned(out, 16, "out");
   check_extent(out, R, ldo, No, "out");
   tdg::EnsembleArgs a{};
-  check_members(logits, V, weights, R, out.device(), "ensemble_logprobs", a.x, a.ldl, a.logw);
+  check_members(logits, V, weights, false, R, out.device(), "ensemble_logprobs", "logits", true, &a.mem);
   a.out = (uint16_t*)out.data_ptr();
   a.M = (int)M;
   a.R = (int)R;
@@ -258,8 +230,6 @@ void score_tokens(const std::vector<Tensor>& logits, int64_t V, const std::vecto
   const int64_t M = (int64_t)logits.size();
   TORCH_CHECK(M >= 1 && M <= tdg::ENSEMBLE_MAX, "score_tokens: 1 to ", tdg::ENSEMBLE_MAX,
               " members, got ", M);
-  TORCH_CHECK((int64_t)weights.size() == M, "score_tokens: ", weights.size(), " weights for ", M,
-              " members");
   TORCH_CHECK(V >= 1 && V <= 65536, "score_tokens: V must be in [1, 65536], got ", V);
   TORCH_CHECK(logits[0].dim() == 2, "every member's logits must be [R, >= V], rows contiguous");
   const int64_t R = logits[0].size(0);
@@ -278,7 +248,7 @@ void score_tokens(const std::vector<Tensor>& logits, int64_t V, const std::vecto
                 "tok_lp / top_lp must be f32 [R] on the members' device");
   }
   tdg::ScoreArgs a{};
-  check_members(logits, V, weights, R, dev, "score_tokens", a.x, a.ldl, a.logw);
+  check_members(logits, V, weights, false, R, dev, "score_tokens", "logits", true, &a.mem);
   a.labels = labels.data_ptr();
   a.lab64 = lt == at::kLong ? 1 : 0;
   a.tok_lp = tok_lp.data_ptr<float>();

@@ -2,8 +2,6 @@
 // label and teacher distributions (loss + in-place gradient), one launch.
 #include "common.h"
 
-#include <cmath>
-
 namespace {
 
 // logits: the student, bf16 [M, ldl] (row stride ldl, any element offset);
@@ -32,25 +30,9 @@ void xent_distill(const Tensor& logits, const std::vector<Tensor>& teachers, int
     check_f32(*row_label, "row_label");
     TORCH_CHECK(row_label->numel() == M && row_label->is_contiguous(), "xent_distill: row_label");
   }
-  TORCH_CHECK(teachers.size() == logw.size(), "xent_distill: ", logw.size(), " weights for ",
-              teachers.size(), " teachers");
   tdg::DistillArgs a{};
   a.T = (int)teachers.size();
-  for (size_t m = 0; m < teachers.size(); ++m) {
-    const Tensor& t = teachers[m];
-    check_bf16(t, "teacher");
-    TORCH_CHECK(t.device() == logits.device(), "xent_distill: teachers and student on one device");
-    TORCH_CHECK(t.dim() == 2 && t.size(0) == M && t.stride(1) == 1 && t.size(1) >= V &&
-                    (t.stride(0) >= t.size(1) || M <= 1) && t.stride(0) < (1LL << 31),
-                "xent_distill: teacher must be [M, >= V] rows");
-    check_extent(t, M, t.stride(0), V, "teacher");
-    TORCH_CHECK(std::isfinite(logw[m]), "xent_distill: weights must be finite and > 0");
-    if (m < (size_t)tdg::DISTILL_MAX) {
-      a.t[m] = static_cast<const uint16_t*>(t.data_ptr());
-      a.ldt[m] = (int)(M > 1 ? t.stride(0) : t.size(1));
-      a.logw[m] = (float)logw[m];
-    }
-  }
+  check_members(teachers, V, logw, true, M, logits.device(), "xent_distill", "teacher", false, &a.t);
   a.x = static_cast<uint16_t*>(logits.data_ptr());
   a.labels = labels.data_ptr();
   a.lab64 = l64;

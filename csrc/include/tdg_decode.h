@@ -62,14 +62,21 @@ struct SampleArgs {
   int R, V, ldl, end_id, pad_id;
 };
 
+// The members of a mixture of distributions over the vocabulary (an ensemble's
+// models, a student's teachers). They ride in the argument block by value: no
+// pointer table on the device, nothing to upload before a launch.
+constexpr int MEMBERS_MAX = 8;
+struct MemberRows {
+  const uint16_t* x[MEMBERS_MAX];  // member m: bf16 [R, ld[m]], the first V columns count
+  float logw[MEMBERS_MAX];         // log of the weights (> 0, sum 1)
+  int ld[MEMBERS_MAX];             // row strides, in elements
+};
+
 // The ensemble's combine step: M members' logits -> the log of the weighted
-// mean of their probabilities, one row per hypothesis. The members ride in
-// the argument block by value: no pointer table on the device.
-constexpr int ENSEMBLE_MAX = 8;
+// mean of their probabilities, one row per hypothesis.
+constexpr int ENSEMBLE_MAX = MEMBERS_MAX;
 struct EnsembleArgs {
-  const uint16_t* x[ENSEMBLE_MAX];  // member m: bf16 [R, ldl[m]], the first V columns count
-  float logw[ENSEMBLE_MAX];         // log of the weights (> 0, sum 1)
-  int ldl[ENSEMBLE_MAX];
+  MemberRows mem;
   uint16_t* out;  // bf16 [R, ldo]: columns [0, V) written, [V, No) set to -inf
   int M, R, V, ldo, No;
 };
@@ -77,9 +84,7 @@ struct EnsembleArgs {
 // Teacher-forced scoring: the same mixture as EnsembleArgs, of which only the
 // label's column and (optionally) the row's largest value are kept.
 struct ScoreArgs {
-  const uint16_t* x[ENSEMBLE_MAX];  // member m: bf16 [R, ldl[m]], the first V columns count
-  float logw[ENSEMBLE_MAX];         // log of the weights (> 0, sum 1)
-  int ldl[ENSEMBLE_MAX];
+  MemberRows mem;
   const void* labels;  // [R] int32, or int64 with lab64
   float* tok_lp;       // [R] mix[r, labels[r]]; 0 on a pad_id row, -inf outside [0, V)
   float* top_lp;       // [R] max_v mix[r, v]; 0 on a pad_id row; null = not wanted

@@ -41,21 +41,16 @@
 // label's column and every other go through one expression (mix_column), so
 // tok_lp >= top_lp is exact. A row whose label is pad_id leaves before its
 // first load.
+//
+// The block reductions, the candidate order and its workgroup arg-best, the
+// 8-value bf16 unpack / pack and the mixture's column load are
+// tdg_vocab_row.h's, shared with xent.hip and distill.hip.
 #include "tdg_api.h"
-#include "tdg_common.h"
+#include "tdg_vocab_row.h"
 
 namespace tdg {
 
 // ---------------------------------------------------------------- decode_attn
-__device__ __forceinline__ void unpack8(const uint4& w, float* f) {
-  const uint32_t u[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = __uint_as_float(u[i] << 16);
-    f[2 * i + 1] = __uint_as_float(u[i] & 0xffff0000u);
-  }
-}
-
 template <int HD>
 __global__ __launch_bounds__(256) void decode_attn_kernel(const DecodeAttnArgs a) {
   constexpr int LPK = HD / 8;    // lanes per key (8 bf16 = 16 bytes each)
@@ -139,40 +134,12 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const DecodeAttnArgs a
   }
   if (lane < LPK) {
     const float inv = 1.f / l;
-    uint4 w;
-    w.x = pack2bf(acc[0] * inv, acc[1] * inv);
-    w.y = pack2bf(acc[2] * inv, acc[3] * inv);
-    w.z = pack2bf(acc[4] * inv, acc[5] * inv);
-    w.w = pack2bf(acc[6] * inv, acc[7] * inv);
-    *reinterpret_cast<uint4*>(orow) = w;
+    *reinterpret_cast<uint4*>(orow) = pack8bf(acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv,
+                                              acc[4] * inv, acc[5] * inv, acc[6] * inv, acc[7] * inv);
   }
 }
 
 // ---------------------------------------------------------------- beam_topk
-constexpr int NO_CAND = 0x7fffffff;
-
-// candidate order: higher value first, equal values by the lower flat index
-__device__ __forceinline__ bool better(float av, int ai, float bv, int bi) {
-  return av > bv || (av == bv && ai < bi);
-}
-
-__device__ __forceinline__ float block_max(float v, float* red) {
-  const float w = wave_max(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-  __syncthreads();
-  const float r = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  const float w = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-  __syncthreads();
-  const float r = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return r;
-}
-
 template <int BEAM>
 __global__ __launch_bounds__(256) void beam_topk_kernel(const BeamTopkArgs a) {
   __shared__ float red[4];
@@ -247,28 +214,10 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const BeamTopkArgs a) {
   for (int k = 0; k < BEAM; ++k) {
     float bv = lv[0];
     int bi = li[0];
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const float ov = __shfl_xor(bv, o);
-      const int oi = __shfl_xor(bi, o);
-      if (better(ov, oi, bv, bi)) {
-        bv = ov;
-        bi = oi;
-      }
-    }
-    if ((tid & 63) == 0) {
-      red[tid >> 6] = bv;
-      redi[tid >> 6] = bi;
-    }
-    __syncthreads();
+    TDG_ARGBEST_WAVES(bv, bi, red, redi)
     bv = red[0];
     bi = redi[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w)
-      if (better(red[w], redi[w], bv, bi)) {
-        bv = red[w];
-        bi = redi[w];
-      }
+    TDG_ARGBEST_FOLD(bv, bi, red, redi)
     __syncthreads();
     if (bi != NO_CAND && li[0] == bi) {  // the winner's owner moves on
 #pragma unroll
@@ -305,11 +254,6 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const BeamTopkArgs a) {
     a.anc_out[(long long)(r0 + b) * a.ld_anc + j] =
         j <= a.t ? a.anc_in[(long long)s_parent[b] * a.ld_anc + j] : r0 + b;
   }
-}
-
-template <int BEAM>
-static void launch_beam_topk(const BeamTopkArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(beam_topk_kernel<BEAM>, dim3(a.B), dim3(256), 0, st, a);
 }
 
 // ---------------------------------------------------------------- sample_token
@@ -477,27 +421,9 @@ __global__ __launch_bounds__(256) void sample_token_kernel(const SampleArgs a) {
       }
     }
   });
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const float ov = __shfl_xor(bv, o);
-    const int oi = __shfl_xor(bi, o);
-    if (better(ov, oi, bv, bi)) {
-      bv = ov;
-      bi = oi;
-    }
-  }
-  if ((tid & 63) == 0) {
-    red[tid >> 6] = bv;
-    redi[tid >> 6] = bi;
-  }
-  __syncthreads();
+  TDG_ARGBEST_WAVES(bv, bi, red, redi)
   if (tid == 0) {
-#pragma unroll
-    for (int w = 1; w < 4; ++w)
-      if (better(red[w], redi[w], bv, bi)) {
-        bv = red[w];
-        bi = redi[w];
-      }
+    TDG_ARGBEST_FOLD(bv, bi, red, redi)
     if (bi == NO_CAND) {  // no comparable key (NaN logits or temperature): a dead row
       put(a.pad_id, -INFINITY, 1);
     } else {
@@ -589,41 +515,25 @@ __global__ __launch_bounds__(256) void ensemble_logprobs_kernel(const EnsembleAr
   const int tid = threadIdx.x, r = blockIdx.x, V = a.V;
   const uint16_t* x[M];
 #pragma unroll
-  for (int m = 0; m < M; ++m) x[m] = a.x[m] + (long long)r * a.ldl[m];
+  for (int m = 0; m < M; ++m) x[m] = a.mem.x[m] + (long long)r * a.mem.ld[m];
 
   float gm[M], off[M];
-  member_offsets<M>(x, a.logw, V, red, gm, off);
+  member_offsets<M>(x, a.mem.logw, V, red, gm, off);
 
   // pass 2: out = log sum_m exp(x_m + off_m); the columns [V, No) get -inf
   uint16_t* const orow = a.out + (long long)r * a.ldo;
   for (int c = tid * 8; c < a.No; c += 2048) {
     float am[M][8], o[8];
     if (c < V) {
-#pragma unroll
-      for (int m = 0; m < M; ++m) {
-        unpack8(*reinterpret_cast<const uint4*>(x[m] + c), am[m]);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          am[m][i] = (c + i < V && am[m][i] > -INFINITY) ? am[m][i] + off[m] : -INFINITY;
-      }
+      TDG_MIX_LOAD(am, x, off, c)
 #pragma unroll
       for (int i = 0; i < 8; ++i) o[i] = mix_column<M>([&](int m) { return am[m][i]; });
     } else {
 #pragma unroll
       for (int i = 0; i < 8; ++i) o[i] = -INFINITY;
     }
-    uint4 w;
-    w.x = pack2bf(o[0], o[1]);
-    w.y = pack2bf(o[2], o[3]);
-    w.z = pack2bf(o[4], o[5]);
-    w.w = pack2bf(o[6], o[7]);
-    *reinterpret_cast<uint4*>(orow + c) = w;
+    *reinterpret_cast<uint4*>(orow + c) = pack8bf(o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7]);
   }
-}
-
-template <int M>
-static void launch_ensemble(const EnsembleArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(ensemble_logprobs_kernel<M>, dim3(a.R), dim3(256), 0, st, a);
 }
 
 template <int M>
@@ -642,10 +552,10 @@ __global__ __launch_bounds__(256) void score_tokens_kernel(const ScoreArgs a) {
   }
   const uint16_t* x[M];
 #pragma unroll
-  for (int m = 0; m < M; ++m) x[m] = a.x[m] + (long long)r * a.ldl[m];
+  for (int m = 0; m < M; ++m) x[m] = a.mem.x[m] + (long long)r * a.mem.ld[m];
 
   float gm[M], off[M];
-  member_offsets<M>(x, a.logw, V, red, gm, off);
+  member_offsets<M>(x, a.mem.logw, V, red, gm, off);
 
   if (tid == 0) {  // the label's column: M scalar loads
     float t = -INFINITY;
@@ -672,13 +582,7 @@ __global__ __launch_bounds__(256) void score_tokens_kernel(const ScoreArgs a) {
     float best = -INFINITY;
     for (int c = tid * 8; c < V; c += 2048) {
       float am[M][8];
-#pragma unroll
-      for (int m = 0; m < M; ++m) {
-        unpack8(*reinterpret_cast<const uint4*>(x[m] + c), am[m]);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          am[m][i] = (c + i < V && am[m][i] > -INFINITY) ? am[m][i] + off[m] : -INFINITY;
-      }
+      TDG_MIX_LOAD(am, x, off, c)
 #pragma unroll
       for (int i = 0; i < 8; ++i) best = fmaxf(best, mix_column<M>([&](int m) { return am[m][i]; }));
     }
@@ -686,11 +590,6 @@ __global__ __launch_bounds__(256) void score_tokens_kernel(const ScoreArgs a) {
     best = block_max(best, red[0]);
     if (tid == 0) a.top_lp[r] = best;
   }
-}
-
-template <int M>
-static void launch_score(const ScoreArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(score_tokens_kernel<M>, dim3(a.R), dim3(256), 0, st, a);
 }
 
 }  // namespace tdg
@@ -721,16 +620,9 @@ int tdg_decode_attn(const tdg::DecodeAttnArgs* a, int hd, hipStream_t st) {
 int tdg_beam_topk(const tdg::BeamTopkArgs* a, hipStream_t st) {
   if (a->beam < 1 || a->beam > 8 || a->V < 1 || a->V > 65536) return -1;
   if (a->B <= 0) return 0;
-  switch (a->beam) {
-    case 1: tdg::launch_beam_topk<1>(*a, st); break;
-    case 2: tdg::launch_beam_topk<2>(*a, st); break;
-    case 3: tdg::launch_beam_topk<3>(*a, st); break;
-    case 4: tdg::launch_beam_topk<4>(*a, st); break;
-    case 5: tdg::launch_beam_topk<5>(*a, st); break;
-    case 6: tdg::launch_beam_topk<6>(*a, st); break;
-    case 7: tdg::launch_beam_topk<7>(*a, st); break;
-    default: tdg::launch_beam_topk<8>(*a, st); break;
-  }
+  tdg::dispatch_upto<8>(a->beam, [&](auto n) {
+    hipLaunchKernelGGL(tdg::beam_topk_kernel<decltype(n)::value>, dim3(a->B), dim3(256), 0, st, *a);
+  });
   return 0;
 }
 
@@ -763,16 +655,9 @@ int tdg_sample_token(const tdg::SampleArgs* a, hipStream_t st) {
 int tdg_ensemble_logprobs(const tdg::EnsembleArgs* a, hipStream_t st) {
   if (a->M < 1 || a->M > tdg::ENSEMBLE_MAX || a->V < 1 || a->V > 65536) return -1;
   if (a->R <= 0) return 0;
-  switch (a->M) {
-    case 1: tdg::launch_ensemble<1>(*a, st); break;
-    case 2: tdg::launch_ensemble<2>(*a, st); break;
-    case 3: tdg::launch_ensemble<3>(*a, st); break;
-    case 4: tdg::launch_ensemble<4>(*a, st); break;
-    case 5: tdg::launch_ensemble<5>(*a, st); break;
-    case 6: tdg::launch_ensemble<6>(*a, st); break;
-    case 7: tdg::launch_ensemble<7>(*a, st); break;
-    default: tdg::launch_ensemble<8>(*a, st); break;
-  }
+  tdg::dispatch_upto<tdg::ENSEMBLE_MAX>(a->M, [&](auto n) {
+    hipLaunchKernelGGL(tdg::ensemble_logprobs_kernel<decltype(n)::value>, dim3(a->R), dim3(256), 0, st, *a);
+  });
   return 0;
 }
 
@@ -785,16 +670,9 @@ int tdg_ensemble_logprobs(const tdg::EnsembleArgs* a, hipStream_t st) {
 int tdg_score_tokens(const tdg::ScoreArgs* a, hipStream_t st) {
   if (a->M < 1 || a->M > tdg::ENSEMBLE_MAX || a->V < 1 || a->V > 65536) return -1;
   if (a->R <= 0) return 0;
-  switch (a->M) {
-    case 1: tdg::launch_score<1>(*a, st); break;
-    case 2: tdg::launch_score<2>(*a, st); break;
-    case 3: tdg::launch_score<3>(*a, st); break;
-    case 4: tdg::launch_score<4>(*a, st); break;
-    case 5: tdg::launch_score<5>(*a, st); break;
-    case 6: tdg::launch_score<6>(*a, st); break;
-    case 7: tdg::launch_score<7>(*a, st); break;
-    default: tdg::launch_score<8>(*a, st); break;
-  }
+  tdg::dispatch_upto<tdg::ENSEMBLE_MAX>(a->M, [&](auto n) {
+    hipLaunchKernelGGL(tdg::score_tokens_kernel<decltype(n)::value>, dim3(a->R), dim3(256), 0, st, *a);
+  });
   return 0;
 }
 

@@ -13,21 +13,15 @@
 // [V, ldl) of the student are written as zero; teacher columns >= V never
 // reach a result. A teacher's softmax is formed as exp((z - max) - (log sum -
 // log w)): the difference of two bf16 logits is exact in f32, so q keeps the
-// relative accuracy of exp where it is not negligible.
+// relative accuracy of exp where it is not negligible. The student's own
+// probability is formed the same way, exp((x - max) - log sum), where xent.hip
+// forms exp(x - lse): the two kernels share their steps (tdg_vocab_row.h), not
+// their arithmetic, and stay two kernels.
 #include "tdg_api.h"
 #include "tdg_common.h"
-#include "tdg_rowloss.h"
+#include "tdg_vocab_row.h"
 
 namespace tdg {
-
-// (m, s) of the whole wave in every lane
-__device__ __forceinline__ void wave_merge(float& m, float& s) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    merge(m, s, m2, s2);
-  }
-}
 
 // Register arm: padded rows of <= 256 * 8 * NCH columns, every row of the
 // student and of the teachers on a 16-byte boundary. The student's NCH chunks
@@ -50,11 +44,7 @@ __global__ __launch_bounds__(256) void distill_reg_kernel(const DistillArgs a) {
   const float alpha = a.alpha, smoothing = a.smoothing;
   const bool mix = valid && alpha > 0.f;  // the same in every thread of the row
   short8_t raw[NCH];
-#pragma unroll
-  for (int k = 0; k < NCH; ++k) {
-    const int ch = tid + 256 * k;
-    if (ch < nch) raw[k] = *reinterpret_cast<const short8_t*>(x + 8 * ch);
-  }
+  TDG_REG_LOAD(raw, x, nch)
   const float xl = bf2f(x[min(max(lab, 0), V - 1)]);  // read before any thread overwrites the row
 
   float q[NCH][8];
@@ -64,7 +54,7 @@ __global__ __launch_bounds__(256) void distill_reg_kernel(const DistillArgs a) {
     for (int e = 0; e < 8; ++e) q[k][e] = 0.f;
   if (mix) {
     for (int t = 0; t < a.T; ++t) {
-      const bf16_t* z = a.t[t] + (size_t)row * a.ldt[t];
+      const bf16_t* z = a.t.x[t] + (size_t)row * a.t.ld[t];
       short8_t tr[NCH];
 #pragma unroll
       for (int k = 0; k < NCH; ++k) {
@@ -72,79 +62,25 @@ __global__ __launch_bounds__(256) void distill_reg_kernel(const DistillArgs a) {
         if (c0 < V) tr[k] = *reinterpret_cast<const short8_t*>(z + c0);
       }
       float tm = -INFINITY, ts = 0.f;
-#pragma unroll
-      for (int k = 0; k < NCH; ++k) {
-        const int c0 = 8 * (tid + 256 * k);
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (c0 + e < V) tm = fmaxf(tm, bf2f((bf16_t)tr[k][e]));
-      }
-#pragma unroll
-      for (int k = 0; k < NCH; ++k) {
-        const int c0 = 8 * (tid + 256 * k);
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (c0 + e < V) ts += __expf(bf2f((bf16_t)tr[k][e]) - tm);
-      }
+      TDG_REG_COLUMNS(tr, tm = fmaxf(tm, v);)
+      TDG_REG_COLUMNS(tr, ts += __expf(v - tm);)
       wave_merge(tm, ts);
       if (lane == 0) { t_m[t][w] = tm; t_s[t][w] = ts; }
       __syncthreads();  // slots of teacher t are written once: no second barrier
       tm = t_m[t][0]; ts = t_s[t][0];
 #pragma unroll
       for (int k = 1; k < 4; ++k) merge(tm, ts, t_m[t][k], t_s[t][k]);
-      const float off = __logf(ts) - a.logw[t];
-#pragma unroll
-      for (int k = 0; k < NCH; ++k) {
-        const int c0 = 8 * (tid + 256 * k);
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (c0 + e < V) q[k][e] += __expf((bf2f((bf16_t)tr[k][e]) - tm) - off);
-      }
+      const float off = __logf(ts) - a.t.logw[t];
+      TDG_REG_COLUMNS(tr, q[k][e] += __expf((v - tm) - off);)
     }
   }
 
   // student: max + first argmax + sum of logits, then sum-exp and sum q x
   float m = -INFINITY, sumx = 0.f;
-  int bi = 0x7fffffff;
-#pragma unroll
-  for (int k = 0; k < NCH; ++k) {
-    const int c0 = 8 * (tid + 256 * k);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      if (c0 + e < V) {
-        const float v = bf2f((bf16_t)raw[k][e]);
-        sumx += v;
-        if (v > m) { m = v; bi = c0 + e; }
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64);
-    const int i2 = __shfl_xor(bi, o, 64);
-    TDG_ARGMAX_TAKE(m, bi, m2, i2)
-    sumx += __shfl_xor(sumx, o, 64);
-  }
-  if (lane == 0) { r_m[w] = m; r_i[w] = bi; r_x[w] = sumx; }
-  __syncthreads();
-  m = r_m[0]; bi = r_i[0]; sumx = r_x[0];
-#pragma unroll
-  for (int k = 1; k < 4; ++k) {
-    TDG_ARGMAX_TAKE(m, bi, r_m[k], r_i[k])
-    sumx += r_x[k];
-  }
+  int bi = NO_CAND;
+  TDG_REG_MAX_SUMX(raw, m, bi, sumx, r_m, r_i, r_x)
   float se = 0.f, qx = 0.f;
-#pragma unroll
-  for (int k = 0; k < NCH; ++k) {
-    const int c0 = 8 * (tid + 256 * k);
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      if (c0 + e < V) {
-        const float v = bf2f((bf16_t)raw[k][e]);
-        se += __expf(v - m);
-        qx += q[k][e] * v;
-      }
-  }
+  TDG_REG_COLUMNS(raw, se += __expf(v - m); qx += q[k][e] * v;)
   se = wave_sum(se);
   qx = wave_sum(qx);
   if (lane == 0) { r_s[w] = se; r_q[w] = qx; }
@@ -155,7 +91,7 @@ __global__ __launch_bounds__(256) void distill_reg_kernel(const DistillArgs a) {
   if (tid == 0) {
     float lab_loss = 0.f, loss = 0.f;
     if (valid) {
-      lab_loss = (1.f - smoothing) * (lse - xl) + smoothing * (lse - sumx / (float)V);
+      lab_loss = label_loss(lse, xl, sumx, V, smoothing);
       loss = lab_loss;
       if (mix) loss = (1.f - alpha) * lab_loss + alpha * (lse - ((r_q[0] + r_q[1]) + (r_q[2] + r_q[3])));
     }
@@ -168,23 +104,9 @@ __global__ __launch_bounds__(256) void distill_reg_kernel(const DistillArgs a) {
   const float oma = 1.f - alpha;
   const float off = smoothing / (float)V;
   const WtBuf wt(a.x, (size_t)gridDim.x * ldl * sizeof(bf16_t));  // one row per block
-#pragma unroll
-  for (int k = 0; k < NCH; ++k) {
-    const int ch = tid + 256 * k;
-    if (ch >= nch) continue;
-    const int c0 = 8 * ch;
-    short8_t g;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int c = c0 + e;
-      float gv = 0.f;
-      if (c < V && valid)
-        gv = (__expf((bf2f((bf16_t)raw[k][e]) - m) - lsr) -
-              oma * (off + (c == lab ? 1.f - smoothing : 0.f)) - alpha * q[k][e]) * scale;
-      g[e] = pack_bf(gv);
-    }
-    wt.st16(x + c0, g);
-  }
+  TDG_REG_STORE_GRAD(raw, x, nch, wt, valid,
+                     (__expf((v - m) - lsr) - oma * (off + (c == lab ? 1.f - smoothing : 0.f)) -
+                      alpha * q[k][e]) * scale)
 }
 
 // Generic arm: any row stride and any (2-byte) alignment of the student and
@@ -207,7 +129,7 @@ __global__ __launch_bounds__(256) void distill_kernel(const DistillArgs a) {
   const float xl = bf2f(x[min(max(lab, 0), V - 1)]);  // read before any thread overwrites the row
 
   float m = -INFINITY, s = 0.f, bv = -INFINITY, sumx = 0.f;
-  int bi = 0x7fffffff;
+  int bi = NO_CAND;
   for (int c = tid; c < V; c += 256) {
     const float v = bf2f(x[c]);
     if (v > m) {
@@ -218,19 +140,11 @@ __global__ __launch_bounds__(256) void distill_kernel(const DistillArgs a) {
     sumx += v;
     if (v > bv) { bv = v; bi = c; }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    merge(m, s, m2, s2);
-    sumx += __shfl_xor(sumx, o, 64);
-    const float bv2 = __shfl_xor(bv, o, 64);
-    const int bi2 = __shfl_xor(bi, o, 64);
-    TDG_ARGMAX_TAKE(bv, bi, bv2, bi2)
-  }
+  TDG_ROW_WAVE_REDUCE(m, s, bv, bi, sumx)
   if (lane == 0) { sm[w] = m; ss[w] = s; sv[w] = bv; si[w] = bi; sx[w] = sumx; }
   if (mix) {
     for (int t = 0; t < T; ++t) {
-      const bf16_t* z = a.t[t] + (size_t)row * a.ldt[t];
+      const bf16_t* z = a.t.x[t] + (size_t)row * a.t.ld[t];
       float tm = -INFINITY, ts = 0.f;
       for (int c = tid; c < V; c += 256) {
         const float v = bf2f(z[c]);
@@ -245,13 +159,7 @@ __global__ __launch_bounds__(256) void distill_kernel(const DistillArgs a) {
     }
   }
   __syncthreads();  // every read of x above is done; the partials are visible
-  m = sm[0]; s = ss[0]; bv = sv[0]; bi = si[0]; sumx = sx[0];
-#pragma unroll
-  for (int k = 1; k < 4; ++k) {
-    merge(m, s, sm[k], ss[k]);
-    sumx += sx[k];
-    TDG_ARGMAX_TAKE(bv, bi, sv[k], si[k])
-  }
+  TDG_ROW_BLOCK_FOLD(m, s, bv, bi, sumx, sm, ss, sv, si, sx)
   const float lsr = __logf(s);
   const float lse = m + lsr;
   float qsum = 0.f;
@@ -261,14 +169,14 @@ __global__ __launch_bounds__(256) void distill_kernel(const DistillArgs a) {
 #pragma unroll
       for (int k = 1; k < 4; ++k) merge(tm, ts, t_m[tid][k], t_s[tid][k]);
       t_max[tid] = tm;
-      t_off[tid] = __logf(ts) - a.logw[tid];
+      t_off[tid] = __logf(ts) - a.t.logw[tid];
     }
     __syncthreads();
     float qx = 0.f;
     for (int c = tid; c < V; c += 256) {
       float qv = 0.f;
       for (int t = 0; t < T; ++t)
-        qv += __expf((bf2f(a.t[t][(size_t)row * a.ldt[t] + c]) - t_max[t]) - t_off[t]);
+        qv += __expf((bf2f(a.t.x[t][(size_t)row * a.t.ld[t] + c]) - t_max[t]) - t_off[t]);
       qx += qv * bf2f(x[c]);
     }
     qx = wave_sum(qx);
@@ -279,7 +187,7 @@ __global__ __launch_bounds__(256) void distill_kernel(const DistillArgs a) {
   if (tid == 0) {
     float lab_loss = 0.f, loss = 0.f;
     if (valid) {
-      lab_loss = (1.f - smoothing) * (lse - xl) + smoothing * (lse - sumx / (float)V);
+      lab_loss = label_loss(lse, xl, sumx, V, smoothing);
       loss = mix ? (1.f - alpha) * lab_loss + alpha * (lse - qsum) : lab_loss;
     }
     a.row_loss[row] = loss;
@@ -296,29 +204,11 @@ __global__ __launch_bounds__(256) void distill_kernel(const DistillArgs a) {
       float qv = 0.f;
       if (mix)
         for (int t = 0; t < T; ++t)
-          qv += __expf((bf2f(a.t[t][(size_t)row * a.ldt[t] + c]) - t_max[t]) - t_off[t]);
+          qv += __expf((bf2f(a.t.x[t][(size_t)row * a.t.ld[t] + c]) - t_max[t]) - t_off[t]);
       g = (__expf((bf2f(x[c]) - m) - lsr) - oma * (off + (c == lab ? 1.f - smoothing : 0.f)) - alpha * qv) *
           scale;
     }
     x[c] = f2bf(g);
-  }
-}
-
-template <typename LabT>
-static void launch_distill(const DistillArgs& a, bool reg, hipStream_t st) {
-  const dim3 grid(a.M), block(256);
-  if (reg) {
-    const int nch = cdiv(a.ldl / 8, 256);
-    if (nch <= 1)
-      hipLaunchKernelGGL((distill_reg_kernel<LabT, 1>), grid, block, 0, st, a);
-    else if (nch == 2)
-      hipLaunchKernelGGL((distill_reg_kernel<LabT, 2>), grid, block, 0, st, a);
-    else if (nch == 3)
-      hipLaunchKernelGGL((distill_reg_kernel<LabT, 3>), grid, block, 0, st, a);
-    else
-      hipLaunchKernelGGL((distill_reg_kernel<LabT, 4>), grid, block, 0, st, a);
-  } else {
-    hipLaunchKernelGGL(distill_kernel<LabT>, grid, block, 0, st, a);
   }
 }
 
@@ -337,13 +227,18 @@ extern "C" int tdg_xent_distill(const tdg::DistillArgs* a, hipStream_t st) {
   if (a->ldl < a->V) return -2;
   bool reg = a->ldl % 8 == 0 && a->ldl <= 256 * 8 * 4 && (reinterpret_cast<uintptr_t>(a->x) & 15) == 0;
   for (int t = 0; t < a->T; ++t) {
-    if (a->ldt[t] < a->V || !a->t[t]) return -2;
-    reg = reg && a->ldt[t] % 8 == 0 && (reinterpret_cast<uintptr_t>(a->t[t]) & 15) == 0;
+    if (a->t.ld[t] < a->V || !a->t.x[t]) return -2;
+    reg = reg && a->t.ld[t] % 8 == 0 && (reinterpret_cast<uintptr_t>(a->t.x[t]) & 15) == 0;
   }
   if (a->M <= 0) return 0;
-  if (a->lab64)
-    tdg::launch_distill<long long>(*a, reg, st);
-  else
-    tdg::launch_distill<int>(*a, reg, st);
+  tdg::dispatch_labels(a->lab64, [&](auto l) {
+    using LabT = decltype(l);
+    const auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(a->M), dim3(256), 0, st, *a); };
+    if (reg)
+      tdg::dispatch_upto<4>(tdg::cdiv(a->ldl / 8, 256),
+                            [&](auto n) { launch(tdg::distill_reg_kernel<LabT, decltype(n)::value>); });
+    else
+      launch(tdg::distill_kernel<LabT>);
+  });
   return 0;
 }

@@ -10,10 +10,12 @@
 // the vocabulary, then a second pass (row is L2-resident) writes
 //   dlogits = (softmax - onehot_smoothed) * scale   (scale = 1/(ntok*workers))
 // in place, or 0 for pad rows. Columns in [V, ldl) are zeroed so the padded
-// logits buffer can feed the dgrad / wgrad GEMMs directly.
+// logits buffer can feed the dgrad / wgrad GEMMs directly. The steps shared with
+// distill.hip (chunk load, max / argmax / sum pass and its reduce, the online
+// statistics' reduce, the gradient store) are tdg_vocab_row.h's.
 #include "tdg_api.h"
 #include "tdg_common.h"
-#include "tdg_rowloss.h"
+#include "tdg_vocab_row.h"
 
 namespace tdg {
 
@@ -33,7 +35,7 @@ __global__ __launch_bounds__(256) void xent_kernel(bf16_t* __restrict__ logits, 
   const int lab = (int)labels[row];
   // pass 1: max, sum-exp (online), argmax (first max), sum of logits (for smoothing)
   float m = -INFINITY, s = 0.f, bv = -INFINITY, sumx = 0.f;
-  int bi = 0x7fffffff;
+  int bi = NO_CAND;
   for (int c = tid * 2; c < V; c += 512) {
     float v0, v1;
     if (c + 1 < V) {
@@ -54,34 +56,19 @@ __global__ __launch_bounds__(256) void xent_kernel(bf16_t* __restrict__ logits, 
     if (v0 > bv) { bv = v0; bi = c; }
     if (c + 1 < V && v1 > bv) { bv = v1; bi = c + 1; }
   }
-  // wave reduction
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    merge(m, s, m2, s2);
-    sumx += __shfl_xor(sumx, o, 64);
-    const float bv2 = __shfl_xor(bv, o, 64);
-    const int bi2 = __shfl_xor(bi, o, 64);
-    TDG_ARGMAX_TAKE(bv, bi, bv2, bi2)
-  }
+  TDG_ROW_WAVE_REDUCE(m, s, bv, bi, sumx)
   if (lane == 0) { sm[w] = m; ss[w] = s; sv[w] = bv; si[w] = bi; }
   __shared__ float sx[4];
   if (lane == 0) sx[w] = sumx;
   __syncthreads();
-  m = sm[0]; s = ss[0]; bv = sv[0]; bi = si[0]; sumx = sx[0];
-#pragma unroll
-  for (int k = 1; k < 4; ++k) {
-    merge(m, s, sm[k], ss[k]);
-    sumx += sx[k];
-    TDG_ARGMAX_TAKE(bv, bi, sv[k], si[k])
-  }
+  TDG_ROW_BLOCK_FOLD(m, s, bv, bi, sumx, sm, ss, sv, si, sx)
   const float lse = m + __logf(s);
   const bool valid = lab != 0;
   if (tid == 0) {
     float loss = 0.f;
     if (valid) {
       const float xl = bf2f(x[lab]);
-      loss = (1.f - smoothing) * (lse - xl) + smoothing * (lse - sumx / (float)V);
+      loss = label_loss(lse, xl, sumx, V, smoothing);
     }
     row_loss[row] = loss;
     row_correct[row] = (valid && bi == lab) ? 1.f : 0.f;
@@ -130,78 +117,29 @@ __global__ __launch_bounds__(256) void xent_reg_kernel(bf16_t* __restrict__ logi
   const int lab = (int)labels[row];
   const int nch = ldl >> 3;
   short8_t raw[NCH];
-#pragma unroll
-  for (int k = 0; k < NCH; ++k) {
-    const int ch = tid + 256 * k;
-    if (ch < nch) raw[k] = *reinterpret_cast<const short8_t*>(x + 8 * ch);
-  }
+  TDG_REG_LOAD(raw, x, nch)
   const float xl = bf2f(x[lab]);  // read before any thread overwrites the row
   float m = -INFINITY, sumx = 0.f;
-  int bi = 0x7fffffff;
-#pragma unroll
-  for (int k = 0; k < NCH; ++k) {
-    const int c0 = 8 * (tid + 256 * k);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      if (c0 + e < V) {
-        const float v = bf2f((bf16_t)raw[k][e]);
-        sumx += v;
-        if (v > m) { m = v; bi = c0 + e; }
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64);
-    const int i2 = __shfl_xor(bi, o, 64);
-    TDG_ARGMAX_TAKE(m, bi, m2, i2)
-    sumx += __shfl_xor(sumx, o, 64);
-  }
-  if (lane == 0) { r_m[w] = m; r_i[w] = bi; r_x[w] = sumx; }
-  __syncthreads();
-  m = r_m[0]; bi = r_i[0]; sumx = r_x[0];
-#pragma unroll
-  for (int k = 1; k < 4; ++k) {
-    TDG_ARGMAX_TAKE(m, bi, r_m[k], r_i[k])
-    sumx += r_x[k];
-  }
+  int bi = NO_CAND;
+  TDG_REG_MAX_SUMX(raw, m, bi, sumx, r_m, r_i, r_x)
   float se = 0.f;
-#pragma unroll
-  for (int k = 0; k < NCH; ++k) {
-    const int c0 = 8 * (tid + 256 * k);
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      if (c0 + e < V) se += __expf(bf2f((bf16_t)raw[k][e]) - m);
-  }
+  TDG_REG_COLUMNS(raw, se += __expf(v - m);)
   se = wave_sum(se);
   if (lane == 0) r_s[w] = se;
   __syncthreads();
   const float lse = m + __logf(r_s[0] + r_s[1] + r_s[2] + r_s[3]);
   const bool valid = lab != 0;
   if (tid == 0) {
-    row_loss[row] = valid ? (1.f - smoothing) * (lse - xl) + smoothing * (lse - sumx / (float)V) : 0.f;
+    row_loss[row] = valid ? label_loss(lse, xl, sumx, V, smoothing) : 0.f;
     row_correct[row] = (valid && bi == lab) ? 1.f : 0.f;
   }
   if (!write_grad) return;
   const float scale = valid ? 1.f / (fmaxf(ntok[0], 1.f) * workers) : 0.f;
   const float off = smoothing / (float)V;
   const WtBuf wt(logits, (size_t)gridDim.x * ldl * sizeof(bf16_t));  // one row per block
-#pragma unroll
-  for (int k = 0; k < NCH; ++k) {
-    const int ch = tid + 256 * k;
-    if (ch >= nch) continue;
-    const int c0 = 8 * ch;
-    short8_t g;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int c = c0 + e;
-      float gv = 0.f;
-      if (c < V && valid)
-        gv = (__expf(bf2f((bf16_t)raw[k][e]) - lse) - off - (c == lab ? 1.f - smoothing : 0.f)) * scale;
-      g[e] = pack_bf(gv);
-    }
-    wt.st16(x + c0, g);  // write-through: 115 MB of dlogits at Transformer-base
-  }
+  // write-through: 115 MB of dlogits at Transformer-base
+  TDG_REG_STORE_GRAD(raw, x, nch, wt, valid,
+                     (__expf(v - lse) - off - (c == lab ? 1.f - smoothing : 0.f)) * scale)
 }
 
 // ntok = number of non-pad labels
@@ -437,33 +375,18 @@ extern "C" int tdg_prep_batch(const void* src, int S, const void* tgt, int T1, i
 extern "C" int tdg_xent(void* logits, int M, int V, int ldl, const void* labels, int lab64,
                         const float* ntok, float workers, float smoothing, float* row_loss,
                         float* row_correct, int write_grad, hipStream_t st) {
-  const bool aligned = (ldl % 8 == 0) && ((reinterpret_cast<uintptr_t>(logits) & 15) == 0);
-  if (aligned && ldl <= 256 * 8 * 4) {
-#define TDG_XR(NCH)                                                                              \
-  if (lab64)                                                                                    \
-    hipLaunchKernelGGL((xent_reg_kernel<long long, NCH>), dim3(M), dim3(256), 0, st,           \
-                       (bf16_t*)logits, V, ldl, (const long long*)labels, ntok, workers,        \
-                       smoothing, row_loss, row_correct, write_grad);                           \
-  else                                                                                          \
-    hipLaunchKernelGGL((xent_reg_kernel<int, NCH>), dim3(M), dim3(256), 0, st, (bf16_t*)logits, \
-                       V, ldl, (const int*)labels, ntok, workers, smoothing, row_loss,          \
-                       row_correct, write_grad);                                                \
-  return 0;
-    const int nch = cdiv(ldl / 8, 256);
-    if (nch <= 1) { TDG_XR(1) }
-    if (nch == 2) { TDG_XR(2) }
-    if (nch == 3) { TDG_XR(3) }
-    TDG_XR(4)
-#undef TDG_XR
-  }
-  if (lab64)
-    hipLaunchKernelGGL(xent_kernel<long long>, dim3(M), dim3(256), 0, st, (bf16_t*)logits, V, ldl,
-                       (const long long*)labels, ntok, workers, smoothing, row_loss, row_correct,
-                       write_grad);
-  else
-    hipLaunchKernelGGL(xent_kernel<int>, dim3(M), dim3(256), 0, st, (bf16_t*)logits, V, ldl,
-                       (const int*)labels, ntok, workers, smoothing, row_loss, row_correct,
-                       write_grad);
+  const bool reg = ldl % 8 == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0 && ldl <= 256 * 8 * 4;
+  dispatch_labels(lab64, [&](auto l) {
+    using LabT = decltype(l);
+    const auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(M), dim3(256), 0, st, (bf16_t*)logits, V, ldl, (const LabT*)labels,
+                         ntok, workers, smoothing, row_loss, row_correct, write_grad);
+    };
+    if (reg)
+      dispatch_upto<4>(cdiv(ldl / 8, 256), [&](auto n) { launch(xent_reg_kernel<LabT, decltype(n)::value>); });
+    else
+      launch(xent_kernel<LabT>);
+  });
   return 0;
 }
 

@@ -45,17 +45,25 @@ def _pybind_include():
     return pybind11.get_include()
 
 
+def rocm_path() -> str:
+    return os.environ.get("ROCM_PATH", "/opt/rocm")
+
+
+def hip_flags(csrc: Path = CSRC) -> str:
+    """The flags every kernel file is compiled with (scripts/isa_diff.py too)."""
+    return (
+        f"-fPIC -O3 -std=c++17 --offload-arch={ARCH} -I{csrc}/include "
+        "-Wno-unused-result -ffp-contract=fast"
+    )
+
+
 def write_ninja() -> Path:
     BUILD.mkdir(exist_ok=True)
     inc, tlib, abi = _torch_paths()
     py_inc = sysconfig.get_paths()["include"]
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    rocm = rocm_path()
     hipcc = f"{rocm}/bin/hipcc"
     incs = " ".join(f"-I{p}" for p in inc)
-    hip_flags = (
-        f"-fPIC -O3 -std=c++17 --offload-arch={ARCH} -I{CSRC}/include "
-        "-Wno-unused-result -ffp-contract=fast"
-    )
     bind_flags = (
         f"-fPIC -O2 -std=c++17 -x c++ -D__HIP_PLATFORM_AMD__=1 -DUSE_ROCM=1 "
         f"-DTORCH_EXTENSION_NAME=_C -DTORCH_API_INCLUDE_EXTENSION_H "
@@ -73,7 +81,7 @@ def write_ninja() -> Path:
     lines = [
         "ninja_required_version = 1.3",
         f"hipcc = {hipcc}",
-        f"hip_flags = {hip_flags}",
+        f"hip_flags = {hip_flags()}",
         f"bind_flags = {bind_flags}",
         f"native_flags = {native_flags}",
         "rule hip",

@@ -19,6 +19,7 @@ import torch
 
 from tensorflow_distributed_on_gke_amd.models.transformer import Transformer
 from tensorflow_distributed_on_gke_amd.ops.kernels import ENSEMBLE_MAX
+from tensorflow_distributed_on_gke_amd.ops.mixture import normalised_weights
 
 
 class Ensemble:
@@ -37,14 +38,13 @@ class Ensemble:
                 raise ValueError("ensemble members need equal src_vocab / tgt_vocab, got "
                                  f"{(first.cfg.src_vocab, first.cfg.tgt_vocab)} and "
                                  f"{(m.cfg.src_vocab, m.cfg.tgt_vocab)}")
-        w = [1.0] * len(models) if weights is None else [float(x) for x in weights]
-        if len(w) != len(models):
-            raise ValueError(f"{len(w)} weights for {len(models)} ensemble members")
-        if not all(0.0 < x < float("inf") for x in w):
-            raise ValueError(f"ensemble weights must be finite and > 0, got {w}")
-        total = math.fsum(w)
+        if weights is not None:
+            weights = list(weights)
+            if len(weights) != len(models):
+                raise ValueError(f"{len(weights)} weights for {len(models)} ensemble members")
         self.models: List[Transformer] = models
-        self.weights: List[float] = [x / total for x in w]
+        self.weights: List[float] = normalised_weights(
+            len(models), weights, "ensemble weights must be finite and > 0", ValueError)
 
     def __len__(self) -> int:
         return len(self.models)

@@ -9,6 +9,7 @@ import torch
 
 from tensorflow_distributed_on_gke_amd.ops._ext import C
 from tensorflow_distributed_on_gke_amd.ops.kernels.attention import _ref_attn_fwd
+from tensorflow_distributed_on_gke_amd.ops.mixture import normalised_weights
 
 
 def decode_attn(q, k, v, kv_len, scale: float, anc=None, row_map=None, k_new=None, v_new=None):
@@ -195,6 +196,29 @@ def sample_token(logits, V: int, score, fin, end_id: int, pad_id: int, temperatu
 ENSEMBLE_MAX = 8
 
 
+def _mixture_args(who: str, logits_list, V: int, weights):
+    """The member count and vocabulary size in range, or RuntimeError; the
+    weights, normalised."""
+    M = len(logits_list)
+    if not 1 <= M <= ENSEMBLE_MAX:
+        raise RuntimeError(f"{who}: {M} members outside [1, {ENSEMBLE_MAX}]")
+    if not 1 <= V <= 65536:
+        raise RuntimeError(f"{who}: V {V} outside [1, 65536]")
+    return normalised_weights(M, weights, f"{who}: needs {M} finite weights > 0")
+
+
+def _mixture(logits_list, V: int, w) -> torch.Tensor:
+    """The CPU definition of the mixture, f32 [R, V] (`ensemble_logprobs`)."""
+    ninf = float("-inf")
+    rows = []
+    for x, wm in zip(logits_list, w):
+        x = x[:, :V].float()
+        x = torch.where(x > ninf, x, torch.full_like(x, ninf))  # NaN too
+        lse = torch.logsumexp(x, dim=1, keepdim=True)
+        rows.append(torch.where(lse > ninf, x - lse + math.log(wm), torch.full_like(x, ninf)))
+    return torch.logsumexp(torch.stack(rows), dim=0)
+
+
 def ensemble_logprobs(logits_list, V: int, weights=None, out=None):
     """The log of the weighted mean of M members' next-token probabilities.
 
@@ -209,16 +233,7 @@ def ensemble_logprobs(logits_list, V: int, weights=None, out=None):
     16-byte aligned), f32 arithmetic, bf16 output: the rounded mixture, which
     the selection kernels renormalise (csrc/kernels/decode.hip). CPU: the same
     definition in f32, unrounded."""
-    M = len(logits_list)
-    if not 1 <= M <= ENSEMBLE_MAX:
-        raise RuntimeError(f"ensemble_logprobs: {M} members outside [1, {ENSEMBLE_MAX}]")
-    if not 1 <= V <= 65536:
-        raise RuntimeError(f"ensemble_logprobs: V {V} outside [1, 65536]")
-    w = [1.0] * M if weights is None else [float(x) for x in weights]
-    if len(w) != M or not all(0.0 < x < float("inf") for x in w):
-        raise RuntimeError(f"ensemble_logprobs: needs {M} finite weights > 0, got {w}")
-    total = math.fsum(w)
-    w = [x / total for x in w]
+    w = _mixture_args("ensemble_logprobs", logits_list, V, weights)
     first = logits_list[0]
     R = first.shape[0]
     if first.is_cuda:
@@ -227,13 +242,7 @@ def ensemble_logprobs(logits_list, V: int, weights=None, out=None):
         C().ensemble_logprobs(list(logits_list), V, w, out)
         return out
     ninf = float("-inf")
-    rows = []
-    for x, wm in zip(logits_list, w):
-        x = x[:, :V].float()
-        x = torch.where(x > ninf, x, torch.full_like(x, ninf))  # NaN too
-        lse = torch.logsumexp(x, dim=1, keepdim=True)
-        rows.append(torch.where(lse > ninf, x - lse + math.log(wm), torch.full_like(x, ninf)))
-    mix = torch.logsumexp(torch.stack(rows), dim=0)
+    mix = _mixture(logits_list, V, w)
     if out is None:
         out = torch.empty(R, (V + 7) // 8 * 8, dtype=torch.float32)
     if out.shape[0] != R or out.shape[1] < V:
@@ -257,16 +266,7 @@ def score_tokens(logits_list, V: int, labels, weights=None, pad_id: int = 0, wan
     label is a most probable token. GPU: bf16 members as for
     `ensemble_logprobs`, f32 arithmetic and outputs (csrc/kernels/decode.hip
     score_tokens); CPU: the same definition in f32."""
-    M = len(logits_list)
-    if not 1 <= M <= ENSEMBLE_MAX:
-        raise RuntimeError(f"score_tokens: {M} members outside [1, {ENSEMBLE_MAX}]")
-    if not 1 <= V <= 65536:
-        raise RuntimeError(f"score_tokens: V {V} outside [1, 65536]")
-    w = [1.0] * M if weights is None else [float(x) for x in weights]
-    if len(w) != M or not all(0.0 < x < float("inf") for x in w):
-        raise RuntimeError(f"score_tokens: needs {M} finite weights > 0, got {w}")
-    total = math.fsum(w)
-    w = [x / total for x in w]
+    w = _mixture_args("score_tokens", logits_list, V, weights)
     first = logits_list[0]
     R = first.shape[0]
     if labels.dim() != 1 or labels.numel() != R or labels.dtype not in (torch.int32, torch.int64):
@@ -278,13 +278,7 @@ def score_tokens(logits_list, V: int, labels, weights=None, pad_id: int = 0, wan
         C().score_tokens(list(logits_list), V, w, labels, pad_id, tok_lp, top_lp)
         return tok_lp, top_lp
     ninf = float("-inf")
-    rows = []
-    for x, wm in zip(logits_list, w):
-        x = x[:, :V].float()
-        x = torch.where(x > ninf, x, torch.full_like(x, ninf))  # NaN too
-        lse = torch.logsumexp(x, dim=1, keepdim=True)
-        rows.append(torch.where(lse > ninf, x - lse + math.log(wm), torch.full_like(x, ninf)))
-    mix = torch.logsumexp(torch.stack(rows), dim=0)
+    mix = _mixture(logits_list, V, w)
     lab = labels.long()
     ignored = lab == pad_id
     inside = (lab >= 0) & (lab < V)

@@ -8,6 +8,7 @@ from typing import List
 import torch
 
 from tensorflow_distributed_on_gke_amd.ops._ext import C
+from tensorflow_distributed_on_gke_amd.ops.mixture import normalised_weights
 
 
 def xent(logits, V, labels, ntok, workers, smoothing, row_loss, row_correct, write_grad=True):
@@ -23,11 +24,7 @@ DISTILL_MAX = 8
 
 def distill_weights(n: int, weights=None) -> List[float]:
     """n positive teacher weights (default uniform), normalised to sum 1."""
-    w = [1.0] * n if weights is None else [float(x) for x in weights]
-    if len(w) != n or not all(0.0 < x < float("inf") for x in w):
-        raise RuntimeError(f"xent_distill: needs {n} finite weights > 0, got {w}")
-    total = math.fsum(w)
-    return [x / total for x in w]
+    return normalised_weights(n, weights, f"xent_distill: needs {n} finite weights > 0")
 
 
 def distill_target(teachers, V: int, labels, smoothing: float, alpha: float, w) -> torch.Tensor:
