@@ -95,11 +95,14 @@ void decode_attn(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor
   check_err(tdg_decode_attn(&a, (int)hd, stream_of(q)), "tdg decode_attn");
 }
 
-void beam_topk(const Tensor& logits, int64_t V, const Tensor& score, const Tensor& fin,
-               int64_t beam, int64_t end_id, int64_t pad_id, const Tensor& score_out,
-               const Tensor& parent, const Tensor& token, const Tensor& fin_out,
-               const optional<Tensor>& anc_in, const optional<Tensor>& anc_out, int64_t t) {
-  TORCH_CHECK(beam >= 1 && beam <= 8, "beam_topk: beam must be in [1, 8], got ", beam);
+// The operands of one selection step, checked, for a width of at most max_beam
+tdg::BeamTopkArgs beam_args(const Tensor& logits, int64_t V, const Tensor& score, const Tensor& fin,
+                            int64_t beam, int64_t max_beam, int64_t end_id, int64_t pad_id,
+                            const Tensor& score_out, const Tensor& parent, const Tensor& token,
+                            const Tensor& fin_out, const optional<Tensor>& anc_in,
+                            const optional<Tensor>& anc_out, int64_t t) {
+  TORCH_CHECK(beam >= 1 && beam <= max_beam, "beam_topk: beam must be in [1, ", max_beam, "], got ",
+              beam);
   TORCH_CHECK(V >= 1 && V <= 65536, "beam_topk: V must be in [1, 65536], got ", V);
   check_bf16(logits, "logits");
   TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.size(1) >= V,
@@ -144,8 +147,41 @@ void beam_topk(const Tensor& logits, int64_t V, const Tensor& score, const Tenso
     a.ld_anc = (int)anc_in->stride(0);
     a.t = (int)t;
   }
+  return a;
+}
+
+void beam_topk(const Tensor& logits, int64_t V, const Tensor& score, const Tensor& fin,
+               int64_t beam, int64_t end_id, int64_t pad_id, const Tensor& score_out,
+               const Tensor& parent, const Tensor& token, const Tensor& fin_out,
+               const optional<Tensor>& anc_in, const optional<Tensor>& anc_out, int64_t t) {
+  const tdg::BeamTopkArgs a = beam_args(logits, V, score, fin, beam, 8, end_id, pad_id, score_out,
+                                        parent, token, fin_out, anc_in, anc_out, t);
   c10::DeviceGuard g(logits.device());
   check_err(tdg_beam_topk(&a, stream_of(logits)), "tdg beam_topk");
+}
+
+// ws: int32 scratch of at least (2 * beam + 1) * R words on the logits' device
+// -- the candidates' values, their flat indices, the rows' counts
+void beam_topk_wide(const Tensor& logits, int64_t V, const Tensor& score, const Tensor& fin,
+                    int64_t beam, int64_t end_id, int64_t pad_id, const Tensor& score_out,
+                    const Tensor& parent, const Tensor& token, const Tensor& fin_out,
+                    const Tensor& ws, const optional<Tensor>& anc_in,
+                    const optional<Tensor>& anc_out, int64_t t) {
+  tdg::BeamWideArgs w{};
+  w.k = beam_args(logits, V, score, fin, beam, tdg::BEAM_WIDE_MAX, end_id, pad_id, score_out, parent,
+                  token, fin_out, anc_in, anc_out, t);
+  const int64_t R = logits.size(0);
+  check_i32(ws, "ws");
+  TORCH_CHECK(ws.device() == logits.device() && ws.dim() == 1 && ws.is_contiguous() &&
+                  ws.numel() >= (2 * beam + 1) * R,
+              "beam_topk_wide: ws must be int32 [>= ", (2 * beam + 1) * R, "] on the logits' device");
+  TORCH_CHECK(R * beam < (1LL << 31), "beam_topk_wide: too many rows");
+  int* const p = ws.data_ptr<int>();
+  w.ws_val = reinterpret_cast<float*>(p);
+  w.ws_idx = p + R * beam;
+  w.ws_cnt = p + 2 * R * beam;
+  c10::DeviceGuard g(logits.device());
+  check_err(tdg_beam_topk_wide(&w, stream_of(logits)), "tdg beam_topk_wide");
 }
 
 void sample_token(const Tensor& logits, int64_t V, const Tensor& score, const Tensor& fin,
@@ -273,6 +309,10 @@ void def_decode(py::module_& m) {
         py::arg("beam"), py::arg("end_id"), py::arg("pad_id"), py::arg("score_out"),
         py::arg("parent"), py::arg("token"), py::arg("fin_out"), py::arg("anc_in") = py::none(),
         py::arg("anc_out") = py::none(), py::arg("t") = 0);
+  m.def("beam_topk_wide", &beam_topk_wide, py::arg("logits"), py::arg("V"), py::arg("score"),
+        py::arg("fin"), py::arg("beam"), py::arg("end_id"), py::arg("pad_id"), py::arg("score_out"),
+        py::arg("parent"), py::arg("token"), py::arg("fin_out"), py::arg("ws"),
+        py::arg("anc_in") = py::none(), py::arg("anc_out") = py::none(), py::arg("t") = 0);
   m.def("sample_token", &sample_token, py::arg("logits"), py::arg("V"), py::arg("score"),
         py::arg("fin"), py::arg("end_id"), py::arg("pad_id"), py::arg("temperature"),
         py::arg("top_k"), py::arg("top_p"), py::arg("seed"), py::arg("step"), py::arg("row_id"),

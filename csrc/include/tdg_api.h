@@ -67,6 +67,11 @@ int tdg_sample_token(const tdg::SampleArgs* a, hipStream_t st);
 int tdg_ensemble_logprobs(const tdg::EnsembleArgs* a, hipStream_t st);
 int tdg_score_tokens(const tdg::ScoreArgs* a, hipStream_t st);
 
+// -------------------------------------------------------------- beam_wide.hip
+// -1: beam outside [1, 64] or V outside [1, 65536]; -2: a null workspace
+// pointer; nothing launched
+int tdg_beam_topk_wide(const tdg::BeamWideArgs* w, hipStream_t st);
+
 // --------------------------------------------------------------- overlap.hip
 // -1: L outside [1, 512], N or P negative, ld < L; -2: a null operand; nothing
 // launched

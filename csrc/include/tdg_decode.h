@@ -45,6 +45,19 @@ struct BeamTopkArgs {
   int B, beam, V, ldl, end_id, pad_id, ld_anc, t;
 };
 
+// The same step for any width up to BEAM_WIDE_MAX, in two launches: beam_rows
+// leaves every row's best min(beam, candidates) candidates in the workspace,
+// beam_merge picks each sentence's best `beam` of them. Row r owns the slots
+// [r * beam, (r + 1) * beam) of ws_val / ws_idx, of which the first ws_cnt[r]
+// hold a candidate (its value, its flat index slot * V + v), in any order.
+constexpr int BEAM_WIDE_MAX = 64;
+struct BeamWideArgs {
+  BeamTopkArgs k;
+  float* ws_val;  // [R * beam]
+  int* ws_idx;    // [R * beam]
+  int* ws_cnt;    // [R]
+};
+
 // One sampling step (temperature, then top-k, then top-p, then a Gumbel-max
 // draw), one row per hypothesis. Row r draws from the Philox stream of
 // (seed, step, row_id[r]), wherever it sits in the batch.

@@ -45,6 +45,9 @@
 // The block reductions, the candidate order and its workgroup arg-best, the
 // 8-value bf16 unpack / pack and the mixture's column load are
 // tdg_vocab_row.h's, shared with xent.hip and distill.hip.
+// sample_token's key and its row in registers are decode_row.h's, shared with
+// beam_wide.hip: the selection step for widths above beam_topk's 8.
+#include "decode_row.h"
 #include "tdg_api.h"
 #include "tdg_vocab_row.h"
 
@@ -257,65 +260,6 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const BeamTopkArgs a) {
 }
 
 // ---------------------------------------------------------------- sample_token
-// The order-preserving 16-bit key of a bf16 logit: a > b <=> okey(a) > okey(b)
-// for finite values (-0 counts as +0). -inf and NaN get 0, below every kept
-// value: the smallest finite bf16 has key KEY_MIN.
-constexpr uint32_t KEY_MIN = 0x0080u;
-__device__ __forceinline__ uint32_t okey(float f) {
-  if (!(f > -INFINITY)) return 0u;
-  uint32_t b = __float_as_uint(f) >> 16;
-  if (b == 0x8000u) b = 0u;
-  return (b & 0x8000u) ? (~b & 0xffffu) : (b | 0x8000u);
-}
-
-// This thread's columns of a row: 8 at c = 8 tid + 2048 j. NCH > 0: the row
-// has at most NCH such chunks and is read once, into registers; NCH == 0: a row
-// of any length, re-read (from L2) by every pass.
-template <int NCH>
-struct RowRegs {
-  uint4 w[NCH > 0 ? NCH : 1];
-  __device__ __forceinline__ void load(const uint16_t* x, int V) {
-    if constexpr (NCH > 0) {
-#pragma unroll
-      for (int j = 0; j < NCH; ++j) {
-        const int c = threadIdx.x * 8 + j * 2048;
-        w[j] = c < V ? *reinterpret_cast<const uint4*>(x + c) : make_uint4(0, 0, 0, 0);
-      }
-    }
-  }
-  // g(c, e, j): the values e[0..8) of columns c .. c + 7, chunk j (0 if NCH == 0)
-  template <class G>
-  __device__ __forceinline__ void chunks(const uint16_t* x, int V, G g) const {
-    if constexpr (NCH > 0) {
-#pragma unroll
-      for (int j = 0; j < NCH; ++j) {
-        const int c = threadIdx.x * 8 + j * 2048;
-        if (c < V) {
-          float e[8];
-          unpack8(w[j], e);
-          g(c, e, j);
-        }
-      }
-    } else {
-      for (int c = threadIdx.x * 8; c < V; c += 2048) {
-        float e[8];
-        unpack8(*reinterpret_cast<const uint4*>(x + c), e);
-        g(c, e, 0);
-      }
-    }
-  }
-  // f(x[v], slot) for the columns v < V, ascending; slot = 8 j + i names the
-  // column among this thread's (NCH > 0)
-  template <class F>
-  __device__ __forceinline__ void scan(const uint16_t* x, int V, F f) const {
-    chunks(x, V, [&](int c, const float* e, int j) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        if (c + i < V) f(e[i], 8 * j + i);
-    });
-  }
-};
-
 template <int NCH>
 __global__ __launch_bounds__(256) void sample_token_kernel(const SampleArgs a) {
   __shared__ float red[4];

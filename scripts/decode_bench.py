@@ -1,6 +1,6 @@
 """Decoding throughput: greedy_cached vs beam_search(beam=1) vs beam_search(beam=4).
 
-    python scripts/decode_bench.py [--repeats 7] [--kernels]
+    python scripts/decode_bench.py [--repeats 7] [--kernels] [--wide]
 
 `base` preset, random weights, B 64 sentences of S 64 source tokens,
 max_length 64; [END] is masked out of the logits (its output bias is -1e4) so
@@ -9,7 +9,9 @@ run interleaved in one process; reported per variant: the median over the
 repeats of generated tokens / s (B * 64 tokens per run, whatever the beam) and
 the spread (min .. max), with every repeat's time. --kernels adds the per-launch times of the attention
 and selection kernels of one step at mid length (beam_topk, and sample_token on the same rows: plain
-and with top-k and top-p, which add a 16-pass bisection each). Prints one JSON line.
+and with top-k and top-p, which add a 16-pass bisection each). --wide measures the beam widths 4 to 64
+instead: the selection step alone at 32 sentences x 7010 columns against the torch composition that defines
+it, and `Tester.decode` on 32 sentences for 32 steps. Prints one JSON line.
 """
 import argparse
 import json
@@ -96,10 +98,50 @@ def kernel_times(cfg, dev):
     return out
 
 
+WIDTHS = (4, 8, 16, 32, 64)
+
+
+def wide_times(tester, src, dev, repeats):
+    """Per beam width: us per selection step (one launch up to width 8, the
+    row / merge pair above) at 32 sentences x 7010 columns, the same step as
+    torch operations on the GPU (both checked to pick the same candidates),
+    and ms per `Tester.decode` of 32 sentences x 32 steps, interleaved."""
+    from tensorflow_distributed_on_gke_amd.ops.kernels.decode import _beam_topk_torch
+
+    nb, t, out = 32, 16, {}
+    g = torch.Generator().manual_seed(0)
+    for beam in WIDTHS:
+        R = nb * beam
+        lg = (torch.randn(R, 7040, generator=g) * 3.0).to(torch.bfloat16).to(dev)
+        score = (-5.0 * torch.rand(R, generator=g)).to(dev)
+        fin = torch.zeros(R, dtype=torch.int32, device=dev)
+        rows = torch.arange(R, dtype=torch.int32, device=dev)
+        anc = rows.view(R, 1).repeat(1, MAXLEN + 1).contiguous()
+        nxt = torch.empty_like(anc)
+        hip = lambda: K.beam_topk(lg, 7010, score, fin, beam, END, 0, anc=anc, t=t, anc_out=nxt)
+        ref = lambda: _beam_topk_torch(lg, 7010, score, fin, beam, END, 0, anc, t, nxt)
+        a, b = hip(), ref()
+        same = float(((a[1] == b[1]) & (a[2] == b[2])).float().mean())  # near-ties may swap in f32
+        out[f"beam{beam}"] = {"beam_topk_us": _launch_us(hip), "torch_composition_us": _launch_us(ref, iters=20),
+                              "slots_equal_to_torch": round(same, 4)}
+    runs = {beam: (lambda beam=beam: tester.decode(src[:nb], max_length=32, beam=beam)[0]) for beam in WIDTHS}
+    for fn in runs.values():
+        fn()
+    times = {beam: [] for beam in WIDTHS}
+    for _ in range(repeats):
+        for beam, fn in runs.items():
+            times[beam].append(_timed(fn)[0] * 1e3)
+    for beam, ts in times.items():
+        out[f"beam{beam}"]["decode_32x32_ms"] = {"median": round(statistics.median(ts), 2),
+                                                  "min": round(min(ts), 2), "max": round(max(ts), 2)}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--wide", action="store_true")
     args = ap.parse_args()
     if args.repeats < 5:
         ap.error("--repeats must be at least 5")
@@ -111,6 +153,10 @@ def main():
     g = torch.Generator().manual_seed(0)
     src = torch.randint(4, cfg.src_vocab, (B, S), generator=g)
     src[:, 0], src[:, -1] = START, END
+    if args.wide:
+        print(json.dumps({"sentences": 32, "V": 7010, "repeats": args.repeats,
+                          "wide": wide_times(tester, src, dev, args.repeats)}))
+        return
     variants = {
         "greedy_cached": lambda: tester.greedy_cached(src, MAXLEN),
         "beam1": lambda: beam_search(m, src, START, END, beam=1, max_length=MAXLEN)[0],

@@ -366,7 +366,7 @@ def main(argv=None) -> int:
     e = sub.add_parser("test", parents=[common, models])
     e.add_argument("--sentence", action="append", default=None)
     e.add_argument("--max-length", type=int, default=20)
-    e.add_argument("--beam", type=int, default=1, help="beam width (1 = greedy, at most 8)")
+    e.add_argument("--beam", type=int, default=1, help="beam width (1 = greedy, at most 64)")
     e.add_argument("--length-penalty", type=float, default=0.6,
                    help="alpha of the beam ranking score / ((5 + len) / 6) ** alpha")
     e.add_argument("--sample", type=int, default=0, metavar="N",

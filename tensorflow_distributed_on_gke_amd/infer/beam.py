@@ -26,6 +26,7 @@ from tensorflow_distributed_on_gke_amd.infer.ensemble import Ensemble, members
 from tensorflow_distributed_on_gke_amd.infer.step import DecoderStep
 from tensorflow_distributed_on_gke_amd.models.transformer import PAD_ID, Transformer, seq_lengths
 from tensorflow_distributed_on_gke_amd.ops import kernels as K
+from tensorflow_distributed_on_gke_amd.ops.kernels.decode import _beam_topk_torch
 
 
 def length_penalty(length: torch.Tensor, alpha: float) -> torch.Tensor:
@@ -55,8 +56,8 @@ def beam_search(model: Union[Transformer, Ensemble], src: torch.Tensor, start: i
     the combine step and is bitwise that model."""
     if reorder not in ("index", "copy"):
         raise ValueError(f"reorder must be 'index' or 'copy', got {reorder!r}")
-    if not 1 <= beam <= 8:
-        raise ValueError(f"beam must be in [1, 8], got {beam}")
+    if not 1 <= beam <= 64:
+        raise ValueError(f"beam must be in [1, 64], got {beam}")
     models, weights = members(model)
     cfg = models[0].cfg
     dev = models[0].device
@@ -86,12 +87,19 @@ def beam_search(model: Union[Transformer, Ensemble], src: torch.Tensor, start: i
     length = torch.zeros(R, dtype=torch.int64, device=dev)
     hist = torch.full((R, 1), start, dtype=torch.int64, device=dev)
     tok = hist[:, 0]
+    # K.beam_topk's CPU arm stops at the one-launch kernel's width; its
+    # definition in torch operations does not
+    wide_cpu = beam > 8 and torch.device(dev).type != "cuda"
     for t in range(max_length):
         klen = torch.full((R,), t + 1, dtype=torch.int32, device=dev)
         lgs = [st.logits(tok, t, klen, cross_len, row_map=row_map, anc=anc) for st in steps]
         lg = lgs[0] if len(lgs) == 1 else K.ensemble_logprobs(lgs, V, weights)
-        score, parent, token, fin_new, new_anc = K.beam_topk(lg, V, score, fin, beam, end, PAD_ID,
-                                                             anc=anc, t=t, anc_out=nxt_anc)
+        if wide_cpu:
+            score, parent, token, fin_new, new_anc = _beam_topk_torch(lg, V, score, fin, beam, end, PAD_ID,
+                                                                      anc, t, nxt_anc)
+        else:
+            score, parent, token, fin_new, new_anc = K.beam_topk(lg, V, score, fin, beam, end, PAD_ID,
+                                                                 anc=anc, t=t, anc_out=nxt_anc)
         par = parent.long()
         if index:
             anc, nxt_anc = new_anc, anc

@@ -9,6 +9,7 @@ import torch
 
 from tensorflow_distributed_on_gke_amd.ops._ext import C
 from tensorflow_distributed_on_gke_amd.ops.kernels.attention import _ref_attn_fwd
+from tensorflow_distributed_on_gke_amd.ops.kernels.workspace import workspace
 from tensorflow_distributed_on_gke_amd.ops.mixture import normalised_weights
 
 
@@ -65,19 +66,37 @@ def beam_topk(logits, V: int, score, fin, beam: int, end_id: int, pad_id: int, a
     advanced from `anc` (int32 [R, > t + 1]): anc'[r, :t+1] =
     anc[parent[r], :t+1], anc'[r, t+1] = r (None without `anc`), written into
     `anc_out` (a second table, never `anc` itself) when given; later columns
-    are not defined. 1 <= beam <= 8, V <= 65536."""
+    are not defined. V <= 65536. GPU: 1 <= beam <= 64; beam <= 8 is one launch
+    of beam_topk (csrc/kernels/decode.hip), a wider beam the row / merge pair
+    of csrc/kernels/beam_wide.hip, which gives the same bits at any width.
+    CPU: the f32 reference of the one-launch kernel, with its bound, 1 <= beam
+    <= 8 (`_beam_topk_torch` is the same definition at any width)."""
     R = logits.shape[0]
-    if not 1 <= beam <= 8 or not 1 <= V <= 65536:
-        raise RuntimeError(f"beam_topk: beam {beam} outside [1, 8] or V {V} outside [1, 65536]")
+    widest = 64 if logits.is_cuda else 8
+    if not 1 <= beam <= widest or not 1 <= V <= 65536:
+        raise RuntimeError(f"beam_topk: beam {beam} outside [1, {widest}] or V {V} outside [1, 65536]")
     dev = logits.device
     if logits.is_cuda:
         score_out = torch.empty(R, dtype=torch.float32, device=dev)
         parent, token, fin_out = (torch.empty(R, dtype=torch.int32, device=dev) for _ in range(3))
         if anc is not None and anc_out is None:
             anc_out = torch.zeros_like(anc)
-        C().beam_topk(logits, V, score, fin, beam, end_id, pad_id, score_out, parent, token, fin_out,
-                      anc, anc_out, t)
+        if beam <= 8:
+            C().beam_topk(logits, V, score, fin, beam, end_id, pad_id, score_out, parent, token, fin_out,
+                          anc, anc_out, t)
+        else:
+            ws = workspace("beam_wide", (2 * beam + 1) * R, dev, torch.int32)
+            C().beam_topk_wide(logits, V, score, fin, beam, end_id, pad_id, score_out, parent, token,
+                               fin_out, ws, anc, anc_out, t)
         return score_out, parent, token, fin_out, anc_out
+    return _beam_topk_torch(logits, V, score, fin, beam, end_id, pad_id, anc, t, anc_out)
+
+
+def _beam_topk_torch(logits, V: int, score, fin, beam: int, end_id: int, pad_id: int, anc, t: int, anc_out):
+    """The definition of `beam_topk` in torch operations, f32, at any width
+    and on any device: its CPU arm, beam search on the CPU above width 8
+    (infer/beam.py) and the composition scripts/decode_bench.py times."""
+    R, dev = logits.shape[0], logits.device
     B = R // beam
     x = logits[:, :V].float()
     logp = x - torch.logsumexp(x, dim=-1, keepdim=True)
@@ -92,7 +111,7 @@ def beam_topk(logits, V: int, score, fin, beam: int, end_id: int, pad_id: int, a
     order = torch.sort(-flat, dim=-1, stable=True).indices[:, :beam]  # ties: lower flat index
     val = torch.gather(flat, 1, order)
     dead = ~(val > float("-inf"))
-    base = (torch.arange(B) * beam).view(B, 1)
+    base = (torch.arange(B, device=dev) * beam).view(B, 1)
     parent = torch.where(dead, base.expand(B, beam), base + order // V)
     token = torch.where(dead, torch.full_like(order, pad_id), order % V)
     fin_out = dead | (fin.view(R)[parent.view(R)].view(B, beam) != 0) | (token == end_id)
@@ -102,7 +121,7 @@ def beam_topk(logits, V: int, score, fin, beam: int, end_id: int, pad_id: int, a
         if anc_out is None:
             anc_out = torch.zeros_like(anc)
         anc_out[:, : t + 1] = anc[parent.long(), : t + 1]
-        anc_out[:, t + 1] = torch.arange(R, dtype=anc.dtype)
+        anc_out[:, t + 1] = torch.arange(R, dtype=anc.dtype, device=dev)
     return (score_out.reshape(R), parent, token.reshape(R).to(torch.int32),
             fin_out.reshape(R).to(torch.int32), anc_out)
 
