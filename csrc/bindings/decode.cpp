@@ -95,6 +95,26 @@ void decode_attn(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor
   check_err(tdg_decode_attn(&a, (int)hd, stream_of(q)), "tdg decode_attn");
 }
 
+// What a selection step reads, checked for `who` (the prefix of its messages): bf16 logits
+// [R, >= V], rows 16-byte aligned; pad / end id in [0, V); score / score_out f32 [R]
+void check_step_rows(const char* who, const Tensor& logits, int64_t V, int64_t end_id,
+                     int64_t pad_id, const Tensor& score, const Tensor& score_out) {
+  TORCH_CHECK(V >= 1 && V <= 65536, who, ": V must be in [1, 65536], got ", V);
+  check_bf16(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.size(1) >= V,
+              "logits must be [R, >= V], rows contiguous");
+  const int64_t R = logits.size(0), ldl = logits.stride(0);
+  TORCH_CHECK(ldl % 8 == 0 && ldl >= round8(V), who, ": logits row stride must be a multiple of 8");
+  check_aligned(logits, 16, "logits");
+  check_extent(logits, R, ldl, round8(V), "logits");
+  TORCH_CHECK(pad_id >= 0 && pad_id < V && end_id >= 0 && end_id < V, who, ": pad / end id");
+  check_f32(score, "score");
+  check_f32(score_out, "score_out");
+  TORCH_CHECK(score.numel() == R && score.is_contiguous() && score_out.numel() == R &&
+                  score_out.is_contiguous(),
+              "score / score_out must be f32 [R]");
+}
+
 // The operands of one selection step, checked, for a width of at most max_beam
 tdg::BeamTopkArgs beam_args(const Tensor& logits, int64_t V, const Tensor& score, const Tensor& fin,
                             int64_t beam, int64_t max_beam, int64_t end_id, int64_t pad_id,
@@ -103,21 +123,9 @@ tdg::BeamTopkArgs beam_args(const Tensor& logits, int64_t V, const Tensor& score
                             const optional<Tensor>& anc_out, int64_t t) {
   TORCH_CHECK(beam >= 1 && beam <= max_beam, "beam_topk: beam must be in [1, ", max_beam, "], got ",
               beam);
-  TORCH_CHECK(V >= 1 && V <= 65536, "beam_topk: V must be in [1, 65536], got ", V);
-  check_bf16(logits, "logits");
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.size(1) >= V,
-              "logits must be [R, >= V], rows contiguous");
+  check_step_rows("beam_topk", logits, V, end_id, pad_id, score, score_out);
   const int64_t R = logits.size(0), ldl = logits.stride(0);
   TORCH_CHECK(R % beam == 0, "beam_topk: rows ", R, " not a multiple of beam ", beam);
-  TORCH_CHECK(ldl % 8 == 0 && ldl >= round8(V), "beam_topk: logits row stride must be a multiple of 8");
-  check_aligned(logits, 16, "logits");
-  check_extent(logits, R, ldl, round8(V), "logits");
-  TORCH_CHECK(pad_id >= 0 && pad_id < V && end_id >= 0 && end_id < V, "beam_topk: pad / end id");
-  check_f32(score, "score");
-  check_f32(score_out, "score_out");
-  TORCH_CHECK(score.numel() == R && score.is_contiguous() && score_out.numel() == R &&
-                  score_out.is_contiguous(),
-              "score / score_out must be f32 [R]");
   tdg::BeamTopkArgs a{};
   a.logits = (const uint16_t*)logits.data_ptr();
   a.score = score.data_ptr<float>();
@@ -188,27 +196,14 @@ void sample_token(const Tensor& logits, int64_t V, const Tensor& score, const Te
                   int64_t end_id, int64_t pad_id, double temperature, int64_t top_k, double top_p,
                   int64_t seed, int64_t step, const optional<Tensor>& row_id,
                   const Tensor& score_out, const Tensor& token, const Tensor& fin_out) {
-  TORCH_CHECK(V >= 1 && V <= 65536, "sample_token: V must be in [1, 65536], got ", V);
   TORCH_CHECK(std::isfinite(temperature) && temperature > 0 && (float)temperature > 0.f,
               "sample_token: temperature must be finite and > 0, got ", temperature);
   TORCH_CHECK(top_p > 0 && top_p <= 1 && (float)top_p > 0.f,
               "sample_token: top_p must be in (0, 1], got ", top_p);
   TORCH_CHECK(top_k >= 0, "sample_token: top_k must be >= 0, got ", top_k);
-  check_bf16(logits, "logits");
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.size(1) >= V,
-              "logits must be [R, >= V], rows contiguous");
+  check_step_rows("sample_token", logits, V, end_id, pad_id, score, score_out);
   const int64_t R = logits.size(0), ldl = logits.stride(0);
   TORCH_CHECK(R < (1LL << 31) && ldl < (1LL << 31), "sample_token: logits too large");
-  TORCH_CHECK(ldl % 8 == 0 && ldl >= round8(V),
-              "sample_token: logits row stride must be a multiple of 8");
-  check_aligned(logits, 16, "logits");
-  check_extent(logits, R, ldl, round8(V), "logits");
-  TORCH_CHECK(pad_id >= 0 && pad_id < V && end_id >= 0 && end_id < V, "sample_token: pad / end id");
-  check_f32(score, "score");
-  check_f32(score_out, "score_out");
-  TORCH_CHECK(score.numel() == R && score.is_contiguous() && score_out.numel() == R &&
-                  score_out.is_contiguous(),
-              "score / score_out must be f32 [R]");
   tdg::SampleArgs a{};
   a.logits = (const uint16_t*)logits.data_ptr();
   a.score = score.data_ptr<float>();

@@ -29,6 +29,7 @@ from tensorflow_distributed_on_gke_amd.infer.greedy import Tester  # noqa: E402
 from tensorflow_distributed_on_gke_amd.infer.tokenizer import END, START, ByteTokenizer  # noqa: E402
 from tensorflow_distributed_on_gke_amd.models.transformer import Transformer, model_config  # noqa: E402
 from tensorflow_distributed_on_gke_amd.ops import kernels as K  # noqa: E402
+from tensorflow_distributed_on_gke_amd.ops.kernels.decode import beam_topk_torch  # noqa: E402
 
 B, S, MAXLEN = 64, 64, 64
 
@@ -106,8 +107,6 @@ def wide_times(tester, src, dev, repeats):
     row / merge pair above) at 32 sentences x 7010 columns, the same step as
     torch operations on the GPU (both checked to pick the same candidates),
     and ms per `Tester.decode` of 32 sentences x 32 steps, interleaved."""
-    from tensorflow_distributed_on_gke_amd.ops.kernels.decode import _beam_topk_torch
-
     nb, t, out = 32, 16, {}
     g = torch.Generator().manual_seed(0)
     for beam in WIDTHS:
@@ -119,7 +118,7 @@ def wide_times(tester, src, dev, repeats):
         anc = rows.view(R, 1).repeat(1, MAXLEN + 1).contiguous()
         nxt = torch.empty_like(anc)
         hip = lambda: K.beam_topk(lg, 7010, score, fin, beam, END, 0, anc=anc, t=t, anc_out=nxt)
-        ref = lambda: _beam_topk_torch(lg, 7010, score, fin, beam, END, 0, anc, t, nxt)
+        ref = lambda: beam_topk_torch(lg, 7010, score, fin, beam, END, 0, anc, t, nxt)
         a, b = hip(), ref()
         same = float(((a[1] == b[1]) & (a[2] == b[2])).float().mean())  # near-ties may swap in f32
         out[f"beam{beam}"] = {"beam_topk_us": _launch_us(hip), "torch_composition_us": _launch_us(ref, iters=20),

@@ -117,8 +117,6 @@ def cmd_train(args) -> int:
 def _load_tester(args):
     """The Tester of `test` and `score`: the settings' tokenizers and one model
     per --weights prefix (several: an ensemble)."""
-    import torch
-
     from tensorflow_distributed_on_gke_amd.checkpoint import bundle
     from tensorflow_distributed_on_gke_amd.config import load_settings
     from tensorflow_distributed_on_gke_amd.infer.greedy import Tester
@@ -126,7 +124,7 @@ def _load_tester(args):
     from tensorflow_distributed_on_gke_amd.train.loop import build_model
 
     settings = load_settings(args.config if os.path.exists(args.config) else None, args.set)
-    dev = args.device if args.device != "auto" else ("cuda:0" if torch.cuda.is_available() else "cpu")
+    dev = _device(args.device)
     if settings.src_tokenizer and settings.tgt_tokenizer:
         # the WordPiece pair a text-data training run saved (data/text.py); like
         # the reference, the vocabulary sizes come from the tokenizers
@@ -444,16 +442,15 @@ def main(argv=None) -> int:
     if args.cmd == "test":
         if (args.input is None) != (args.output is None) or (args.input and args.sentence):
             ap.error("test: --input and --output go together, without --sentence")
-        if args.beam > 1 and args.sample > 0:
-            ap.error("test: --beam and --sample exclude each other")
-        if args.batch < 1 or args.sample < 0:
-            ap.error("test: --batch must be at least 1 and --sample at least 0")
-        if args.n_best and (args.beam <= 1 or not args.input):
+        if args.batch < 1:
+            ap.error("test: --batch must be at least 1")
+        if args.n_best and not args.input:
             ap.error("test: --n-best lists the hypotheses of --beam N > 1 in file mode (--input)")
-        if args.mbr and max(args.beam, args.sample) < 2:
-            ap.error("test: --mbr selects among candidates: it needs --sample N or --beam N, N >= 2")
-        if args.mbr and args.n_best:
-            ap.error("test: --mbr keeps one hypothesis per source: not with --n-best")
+        from tensorflow_distributed_on_gke_amd.infer.greedy import check_mode
+        try:  # the library's own rules, before any model is built
+            check_mode(beam=args.beam, sample=args.sample, n_best=args.n_best, mbr=args.mbr)
+        except ValueError as e:
+            ap.error(f"test: {e}")
     if args.cmd == "mbr":
         try:  # before anything else runs
             args.groups = _read_candidates(args.input)

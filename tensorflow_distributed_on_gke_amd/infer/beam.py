@@ -22,11 +22,11 @@ from typing import Tuple, Union
 
 import torch
 
-from tensorflow_distributed_on_gke_amd.infer.ensemble import Ensemble, members
-from tensorflow_distributed_on_gke_amd.infer.step import DecoderStep
-from tensorflow_distributed_on_gke_amd.models.transformer import PAD_ID, Transformer, seq_lengths
+from tensorflow_distributed_on_gke_amd.infer.ensemble import Ensemble
+from tensorflow_distributed_on_gke_amd.infer.step import DecoderRows
+from tensorflow_distributed_on_gke_amd.models.transformer import PAD_ID, Transformer
 from tensorflow_distributed_on_gke_amd.ops import kernels as K
-from tensorflow_distributed_on_gke_amd.ops.kernels.decode import _beam_topk_torch
+from tensorflow_distributed_on_gke_amd.ops.kernels.decode import beam_topk_torch
 
 
 def length_penalty(length: torch.Tensor, alpha: float) -> torch.Tensor:
@@ -58,27 +58,13 @@ def beam_search(model: Union[Transformer, Ensemble], src: torch.Tensor, start: i
         raise ValueError(f"reorder must be 'index' or 'copy', got {reorder!r}")
     if not 1 <= beam <= 64:
         raise ValueError(f"beam must be in [1, 64], got {beam}")
-    models, weights = members(model)
-    cfg = models[0].cfg
-    dev = models[0].device
-    src = src.to(dev)
-    B = src.shape[0]
-    R = B * beam
-    V = cfg.tgt_vocab
-    for m in models:
-        if max_length + 1 > m.cfg.max_tgt_len:
-            raise ValueError(f"max_length {max_length} + 1 > positional table {m.cfg.max_tgt_len}")
-    src_len = seq_lengths(src)
-    steps = [DecoderStep(m, src, src_len, R, max_length) for m in models]
-    Tm = max_length + 1
-    rows = torch.arange(R, dtype=torch.int32, device=dev)
-    row_map = torch.div(rows, beam, rounding_mode="floor").to(torch.int32)
-    cross_len = src_len[row_map.long()].to(torch.int32).contiguous()
+    dr = DecoderRows(model, src, beam, max_length)
+    B, R, V, dev = dr.B, dr.R, dr.V, dr.dev
     index = reorder == "index"
     anc = nxt_anc = None
     if index:
-        anc = torch.zeros(R, Tm, dtype=torch.int32, device=dev)
-        anc[:, 0] = rows
+        anc = torch.zeros(R, max_length + 1, dtype=torch.int32, device=dev)
+        anc[:, 0] = dr.rows
         nxt_anc = torch.zeros_like(anc)
     score = torch.full((B, beam), float("-inf"), dtype=torch.float32, device=dev)
     score[:, 0] = 0.0
@@ -89,23 +75,15 @@ def beam_search(model: Union[Transformer, Ensemble], src: torch.Tensor, start: i
     tok = hist[:, 0]
     # K.beam_topk's CPU arm stops at the one-launch kernel's width; its
     # definition in torch operations does not
-    wide_cpu = beam > 8 and torch.device(dev).type != "cuda"
+    select = beam_topk_torch if beam > 8 and dev.type != "cuda" else K.beam_topk
     for t in range(max_length):
-        klen = torch.full((R,), t + 1, dtype=torch.int32, device=dev)
-        lgs = [st.logits(tok, t, klen, cross_len, row_map=row_map, anc=anc) for st in steps]
-        lg = lgs[0] if len(lgs) == 1 else K.ensemble_logprobs(lgs, V, weights)
-        if wide_cpu:
-            score, parent, token, fin_new, new_anc = _beam_topk_torch(lg, V, score, fin, beam, end, PAD_ID,
-                                                                      anc, t, nxt_anc)
-        else:
-            score, parent, token, fin_new, new_anc = K.beam_topk(lg, V, score, fin, beam, end, PAD_ID,
-                                                                 anc=anc, t=t, anc_out=nxt_anc)
+        lg = dr.logits(tok, t, anc=anc)
+        score, parent, token, fin_new, new_anc = select(lg, V, score, fin, beam, end, PAD_ID, anc, t, nxt_anc)
         par = parent.long()
         if index:
             anc, nxt_anc = new_anc, anc
         elif t + 1 < max_length:
-            for st in steps:
-                st.gather(par)
+            dr.gather(par)
         tok = token.long()
         length = length[par] + (fin[par] == 0).long()
         hist = torch.cat([hist[par], tok.view(R, 1)], dim=1)

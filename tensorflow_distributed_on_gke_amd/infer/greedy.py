@@ -18,10 +18,39 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
+from tensorflow_distributed_on_gke_amd.infer.beam import beam_search, length_penalty
 from tensorflow_distributed_on_gke_amd.infer.ensemble import Ensemble, members
+from tensorflow_distributed_on_gke_amd.infer.mbr import mbr_select
+from tensorflow_distributed_on_gke_amd.infer.sample import sample_search
+from tensorflow_distributed_on_gke_amd.infer.score import score_pairs
 from tensorflow_distributed_on_gke_amd.infer.step import DecoderStep
+from tensorflow_distributed_on_gke_amd.infer.tokenizer import after_first_end
 from tensorflow_distributed_on_gke_amd.models.layers import CrossKVFn, EmbedFn, KVGrad, RunCtx
 from tensorflow_distributed_on_gke_amd.models.transformer import PAD_ID, Transformer, seq_lengths
+
+
+def check_mode(beam: int = 1, sample: int = 0, n_best: bool = False, mbr: bool = False, **_) -> None:
+    """The rules between the decoding modes of `Tester.decode`, or ValueError;
+    its other arguments are accepted and do not matter here."""
+    if sample < 0:
+        raise ValueError(f"sample must be >= 0, got {sample}")
+    if sample > 0 and beam > 1:
+        raise ValueError("beam > 1 and sample > 0 exclude each other")
+    if n_best and beam <= 1:
+        raise ValueError("n_best lists the hypotheses of a beam search: it needs beam > 1")
+    if mbr and n_best:
+        raise ValueError("mbr keeps one hypothesis per sentence: it does not go with n_best")
+    if mbr and max(sample, beam) < 2:
+        raise ValueError("mbr selects among candidates: it needs sample >= 2 or beam >= 2")
+
+
+def _append_argmax(out: torch.Tensor, done: torch.Tensor, lg: torch.Tensor, end: int):
+    """The tail of a greedy step: (out with the argmax of lg f32 [B, V] appended, PAD in
+    rows that had ended; whether all have ended now). `done` bool [B] is updated in place."""
+    nxt = lg.argmax(dim=-1)
+    nxt = torch.where(done, torch.full_like(nxt, PAD_ID), nxt)
+    done |= nxt == end
+    return torch.cat([out, nxt.view(-1, 1)], dim=1), bool(done.all())
 
 
 class Tester:
@@ -65,11 +94,8 @@ class Tester:
                 x = layer(x, kv_all, kvh, src_len, tgt_len, rt)
             last = x[:, -1:, :]
             lg = m.project(last.contiguous())[:, : m.cfg.tgt_vocab].float()
-            nxt = lg.argmax(dim=-1)
-            nxt = torch.where(done, torch.full_like(nxt, PAD_ID), nxt)
-            out = torch.cat([out, nxt.view(B, 1)], dim=1)
-            done |= nxt == end
-            if bool(done.all()):
+            out, all_done = _append_argmax(out, done, lg, end)
+            if all_done:
                 break
         return out
 
@@ -91,11 +117,8 @@ class Tester:
         for t in range(max_length):
             klen = torch.full((B,), t + 1, dtype=torch.int32, device=dev)
             lg = step.logits(out[:, -1], t, klen, src_len)[:, : m.cfg.tgt_vocab].float()
-            nxt = lg.argmax(dim=-1)
-            nxt = torch.where(done, torch.full_like(nxt, PAD_ID), nxt)
-            out = torch.cat([out, nxt.view(B, 1)], dim=1)
-            done |= nxt == end
-            if bool(done.all()):
+            out, all_done = _append_argmax(out, done, lg, end)
+            if all_done:
                 break
         return out
 
@@ -125,47 +148,42 @@ class Tester:
         alpha 0, whose score is returned. `mbr`: of the `sample` draws, or of
         the beam's hypotheses, the one of highest expected utility
         (`decode_mbr`), in the n = 1 form, with its model score."""
-        if sample < 0:
-            raise ValueError(f"sample must be >= 0, got {sample}")
-        if sample > 0 and beam > 1:
-            raise ValueError("beam > 1 and sample > 0 exclude each other")
-        if n_best and beam <= 1:
-            raise ValueError("n_best lists the hypotheses of a beam search: it needs beam > 1")
-        start, end = self.tgt_tok.start_end()
+        check_mode(beam=beam, sample=sample, n_best=n_best, mbr=mbr)
         ensemble = isinstance(self.model, Ensemble)
         if ensemble and not kv_cache:
             raise ValueError("an ensemble decodes with the K/V cache: kv_cache=False is not supported")
+        draw = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, row_id0=row_id0)
         if mbr:
-            if n_best:
-                raise ValueError("mbr keeps one hypothesis per sentence: it does not go with n_best")
-            return self.decode_mbr(src, max_length, beam=beam, alpha=alpha, sample=sample,
-                                   temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
-                                   row_id0=row_id0)[:2]
-        if sample > 0:
-            from tensorflow_distributed_on_gke_amd.infer.sample import sample_search
-
-            tokens, scores = sample_search(self.model, src, start, end, n=sample, max_length=max_length,
-                                           temperature=temperature, top_k=top_k, top_p=top_p,
-                                           seed=seed, row_id0=row_id0)
-            return tokens.cpu(), scores.cpu()
-        if beam > 1 or ensemble:
-            from tensorflow_distributed_on_gke_amd.infer.beam import beam_search, length_penalty
-
-            tokens, scores, all_tokens, all_scores = beam_search(
-                self.model, src, start, end, beam=beam, max_length=max_length,
-                alpha=alpha if beam > 1 else 0.0)
+            return self.decode_mbr(src, max_length, beam=beam, alpha=alpha, sample=sample, **draw)[:2]
+        if sample > 0 or beam > 1 or ensemble:
+            tokens, scores, best = self._candidates(src, max_length, beam, alpha if beam > 1 else 0.0,
+                                                    sample, **draw)
             if n_best:
                 # beam_search's own ranking: score / ((5 + len) / 6) ** alpha, len up to
                 # and including [END], the first of equal values first
-                is_end = (all_tokens[:, :, 1:] == end).long()
-                length = (is_end.cumsum(dim=2) - is_end == 0).sum(dim=2)
-                ranked = all_scores / length_penalty(length, alpha)
+                _, end = self.tgt_tok.start_end()
+                length = (~after_first_end(tokens[:, :, 1:], end)).sum(dim=2)
+                ranked = scores / length_penalty(length, alpha)
                 order = torch.sort(-ranked, dim=1, stable=True).indices
-                all_tokens = all_tokens.gather(1, order.unsqueeze(-1).expand_as(all_tokens))
-                return all_tokens.cpu(), all_scores.gather(1, order).cpu()
-            return tokens.cpu().unsqueeze(1), scores.cpu().unsqueeze(1)
+                tokens = tokens.gather(1, order.unsqueeze(-1).expand_as(tokens))
+                scores = scores.gather(1, order)
+            elif best is not None:
+                tokens, scores = best[0].unsqueeze(1), best[1].unsqueeze(1)
+            return tokens.cpu(), scores.cpu()
         out = (self.greedy_cached if kv_cache else self.greedy)(src, max_length).cpu()
         return out.unsqueeze(1), None
+
+    def _candidates(self, src: torch.Tensor, max_length: int, beam: int, alpha: float, sample: int, **draw):
+        """The candidates of a mode, on the device: (tokens int64 [B, n, L], scores f32 [B, n],
+        best). `sample` > 0: each sentence's n = `sample` draws (`draw`: sampling's own arguments),
+        best None. Otherwise its beam's n = `beam` hypotheses and that loop's own best pair."""
+        start, end = self.tgt_tok.start_end()
+        if sample > 0:
+            drawn = sample_search(self.model, src, start, end, n=sample, max_length=max_length, **draw)
+            return (*drawn, None)
+        tokens, scores, all_tokens, all_scores = beam_search(self.model, src, start, end, beam=beam,
+                                                             max_length=max_length, alpha=alpha)
+        return all_tokens, all_scores, (tokens, scores)
 
     def decode_mbr(self, src: torch.Tensor, max_length: int = 20, beam: int = 1, alpha: float = 0.6,
                    sample: int = 0, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
@@ -179,27 +197,11 @@ class Tester:
         src int64 [B, S] -> (tokens int64 [B, 1, 1 + len], the kept
         candidate's model score f32 [B, 1], its expected utility f64 [B]), on
         the CPU."""
-        from tensorflow_distributed_on_gke_amd.infer.mbr import mbr_select
-
-        if sample > 0 and beam > 1:
-            raise ValueError("beam > 1 and sample > 0 exclude each other")
-        if max(sample, beam) < 2:
-            raise ValueError("mbr selects among candidates: it needs sample >= 2 or beam >= 2")
-        start, end = self.tgt_tok.start_end()
-        valid = None
-        if sample > 0:
-            from tensorflow_distributed_on_gke_amd.infer.sample import sample_search
-
-            tokens, scores = sample_search(self.model, src, start, end, n=sample, max_length=max_length,
-                                           temperature=temperature, top_k=top_k, top_p=top_p,
-                                           seed=seed, row_id0=row_id0)
-        else:
-            from tensorflow_distributed_on_gke_amd.infer.beam import beam_search
-
-            _, _, tokens, scores = beam_search(self.model, src, start, end, beam=beam,
-                                               max_length=max_length, alpha=alpha)
-            valid = scores > float("-inf")
-        best, expected = mbr_select(tokens, end, PAD_ID, valid)
+        check_mode(beam=beam, sample=sample, mbr=True)
+        tokens, scores, _ = self._candidates(src, max_length, beam, alpha, sample, temperature=temperature,
+                                             top_k=top_k, top_p=top_p, seed=seed, row_id0=row_id0)
+        valid = None if sample > 0 else scores > float("-inf")
+        best, expected = mbr_select(tokens, self.tgt_tok.start_end()[1], PAD_ID, valid)
         pick = best.view(-1, 1)
         kept = tokens.gather(1, pick.unsqueeze(-1).expand(-1, 1, tokens.shape[2]))
         return kept.cpu(), scores.gather(1, pick).cpu(), expected.gather(1, pick).view(-1).cpu()
@@ -232,10 +234,9 @@ class Tester:
         are the decoding arguments of `decode`. In sample mode line i's rows
         have the identities i * sample .. in the random stream, whichever
         batch the line falls into."""
+        check_mode(**mode)
         n = max(1, mode.get("sample", 0))
         mbr = mode.get("mbr", False)
-        if mbr and mode.get("n_best"):
-            raise ValueError("mbr keeps one hypothesis per sentence: it does not go with n_best")
         lens = [int((self.src_tok.tokenize(s) != PAD_ID).sum()) for s in lines]
         order = sorted(range(len(lines)), key=lambda i: (lens[i], i))
         out: List[List[Tuple[str, float]]] = [[] for _ in lines]
@@ -268,8 +269,6 @@ class Tester:
         are scored `batch` at a time in order of (source length, target
         length), so that a batch pads little. A pair with a side longer than
         the model's positional table is not scored: (nan, 0, [], None)."""
-        from tensorflow_distributed_on_gke_amd.infer.score import score_pairs
-
         if len(sources) != len(targets):
             raise ValueError(f"{len(sources)} sources for {len(targets)} targets")
         src_rows = [self.src_tok.tokenize(s)[0] for s in sources]

@@ -16,6 +16,7 @@ from typing import Optional, Tuple
 
 import torch
 
+from tensorflow_distributed_on_gke_amd.infer.tokenizer import after_first_end
 from tensorflow_distributed_on_gke_amd.ops.kernels.overlap import NGRAM_MAX_L, ngram_matches
 
 
@@ -50,9 +51,9 @@ def candidate_rows(tokens: torch.Tensor, end: int, pad_id: int) -> Tuple[torch.T
     if T == 0:
         return (torch.zeros(B * n, 1, dtype=torch.int32, device=tokens.device),
                 torch.zeros(B * n, dtype=torch.int32, device=tokens.device))
-    before_end = (body == end).long().cumsum(dim=2) == 0
+    content = ~after_first_end(body, end) & (body != end) & (body != pad_id)
     pos = torch.arange(1, T + 1, device=tokens.device)
-    length = (pos * (before_end & (body != pad_id))).max(dim=2).values
+    length = (pos * content).max(dim=2).values
     return body.reshape(B * n, T).to(torch.int32), length.reshape(B * n).to(torch.int32)
 
 

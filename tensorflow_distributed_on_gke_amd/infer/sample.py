@@ -18,9 +18,9 @@ from typing import Union
 
 import torch
 
-from tensorflow_distributed_on_gke_amd.infer.ensemble import Ensemble, members
-from tensorflow_distributed_on_gke_amd.infer.step import DecoderStep
-from tensorflow_distributed_on_gke_amd.models.transformer import PAD_ID, Transformer, seq_lengths
+from tensorflow_distributed_on_gke_amd.infer.ensemble import Ensemble
+from tensorflow_distributed_on_gke_amd.infer.step import DecoderRows
+from tensorflow_distributed_on_gke_amd.models.transformer import PAD_ID, Transformer
 from tensorflow_distributed_on_gke_amd.ops import kernels as K
 
 
@@ -46,39 +46,23 @@ def sample_search(model: Union[Transformer, Ensemble], src: torch.Tensor, start:
     combine step and is bitwise that model."""
     if n < 1:
         raise ValueError(f"n must be at least 1, got {n}")
-    models, weights = members(model)
-    cfg = models[0].cfg
-    dev = models[0].device
-    src = src.to(dev)
-    B = src.shape[0]
-    R = B * n
-    V = cfg.tgt_vocab
-    for m in models:
-        if max_length + 1 > m.cfg.max_tgt_len:
-            raise ValueError(f"max_length {max_length} + 1 > positional table {m.cfg.max_tgt_len}")
-    src_len = seq_lengths(src)
-    dec = [DecoderStep(m, src, src_len, R, max_length) for m in models]
-    rows = torch.arange(R, dtype=torch.int32, device=dev)
-    row_map = torch.div(rows, n, rounding_mode="floor").to(torch.int32)
+    dr = DecoderRows(model, src, n, max_length)
+    B, R, V, dev, rows = dr.B, dr.R, dr.V, dr.dev, dr.rows
     if isinstance(row_id0, int):
         row_id = rows.long() + row_id0
     else:  # one base per sentence: its samples are base .. base + n - 1
         base = torch.as_tensor(row_id0, dtype=torch.int64).to(dev)
         if base.shape != (B,):
             raise ValueError(f"row_id0 must be an int or one int per sentence, got shape {tuple(base.shape)}")
-        row_id = base[row_map.long()] + rows.long() % n
+        row_id = base[dr.row_map.long()] + rows.long() % n
     row_id = row_id & 0xFFFFFFFF  # 32 bits of identity, as int32
     row_id = torch.where(row_id >= 2 ** 31, row_id - 2 ** 32, row_id).to(torch.int32)
-    cross_len = src_len[row_map.long()].to(torch.int32).contiguous()
     score = torch.zeros(R, dtype=torch.float32, device=dev)
     fin = torch.zeros(R, dtype=torch.int32, device=dev)
     hist = [torch.full((R,), start, dtype=torch.int64, device=dev)]
     steps = []
     for t in range(max_length):
-        tok = hist[-1]
-        klen = torch.full((R,), t + 1, dtype=torch.int32, device=dev)
-        lgs = [st.logits(tok, t, klen, cross_len, row_map=row_map) for st in dec]
-        lg = lgs[0] if len(lgs) == 1 else K.ensemble_logprobs(lgs, V, weights)
+        lg, lgs = dr.logits(hist[-1], t, want_members=True)
         score, token, fin = K.sample_token(lg, V, score, fin, end, PAD_ID, temperature=temperature,
                                            top_k=top_k, top_p=top_p, seed=seed, step=t, row_id=row_id)
         if return_steps:

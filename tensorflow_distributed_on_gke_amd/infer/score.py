@@ -17,7 +17,7 @@ from typing import List, NamedTuple, Optional, Union
 import torch
 
 from tensorflow_distributed_on_gke_amd.infer.ensemble import Ensemble, members
-from tensorflow_distributed_on_gke_amd.infer.tokenizer import END
+from tensorflow_distributed_on_gke_amd.infer.tokenizer import END, after_first_end
 from tensorflow_distributed_on_gke_amd.models.layers import RunCtx
 from tensorflow_distributed_on_gke_amd.models.transformer import PAD_ID, Transformer
 from tensorflow_distributed_on_gke_amd.ops.kernels.decode import score_tokens
@@ -33,9 +33,7 @@ class Scores(NamedTuple):
 
 def mask_after_end(labels: torch.Tensor, end: int) -> torch.Tensor:
     """labels with every position after the first `end` set to PAD."""
-    is_end = (labels == end).long()
-    after = is_end.cumsum(dim=1) - is_end > 0
-    return labels.masked_fill(after, PAD_ID)
+    return labels.masked_fill(after_first_end(labels, end), PAD_ID)
 
 
 @torch.no_grad()

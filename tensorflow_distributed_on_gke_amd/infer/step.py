@@ -3,20 +3,21 @@
 `DecoderStep` owns, for one `Transformer` and one batch of source sentences,
 the encoder output, the stacked cross-attention K / V, the self-attention K / V
 caches of R rows, and the pass embed -> decoder layers -> `project` for one new
-token per row. The greedy, beam-search and sampling loops (infer/greedy.py,
-infer/beam.py, infer/sample.py) run it once per step; an ensemble
-(infer/ensemble.py) holds one per member and runs them on the same rows. What
-belongs to the hypotheses rather than to a model (the ancestry table, the row
-map, the key counts, scores, history) stays with the loop and is passed in.
+token per row. The cached greedy loop (infer/greedy.py) runs one directly.
+Beam search and sampling (infer/beam.py, infer/sample.py) go through
+`DecoderRows`: one step per member of the model or ensemble (infer/ensemble.py)
+and what the rows of such a loop share whatever it selects. What belongs to
+the hypotheses (the ancestry table, scores, history) stays with the loop.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Union
 
 import torch
 
+from tensorflow_distributed_on_gke_amd.infer.ensemble import Ensemble, members
 from tensorflow_distributed_on_gke_amd.models.layers import LN_EPS, CrossKVFn, KVGrad, RunCtx
-from tensorflow_distributed_on_gke_amd.models.transformer import Transformer
+from tensorflow_distributed_on_gke_amd.models.transformer import Transformer, seq_lengths
 from tensorflow_distributed_on_gke_amd.ops import kernels as K
 from tensorflow_distributed_on_gke_amd.ops.kernels.attention import _ref_attn_fwd
 
@@ -118,3 +119,43 @@ class DecoderStep:
         for li in range(len(self.kcache)):
             self.kcache[li] = self.kcache[li].index_select(0, parent)
             self.vcache[li] = self.vcache[li].index_select(0, parent)
+
+
+class DecoderRows:
+    """The rows of a cached decoding loop: `per_sentence` of them (a beam's hypotheses, a
+    sentence's samples) for each of the B sentences of `src` int64 [B, S], R in all, row r of
+    sentence r // per_sentence, which the cross-attention reads through `row_map`. One
+    `DecoderStep` per member of `model`, all on these rows."""
+
+    def __init__(self, model: Union[Transformer, Ensemble], src: torch.Tensor, per_sentence: int,
+                 max_length: int):
+        self.models, self.weights = members(model)
+        self.dev = dev = self.models[0].device
+        self.V = self.models[0].cfg.tgt_vocab
+        src = src.to(dev)
+        self.B = src.shape[0]
+        self.R = R = self.B * per_sentence
+        for m in self.models:
+            if max_length + 1 > m.cfg.max_tgt_len:
+                raise ValueError(f"max_length {max_length} + 1 > positional table {m.cfg.max_tgt_len}")
+        self.src_len = seq_lengths(src)
+        self.steps = [DecoderStep(m, src, self.src_len, R, max_length) for m in self.models]
+        self.rows = torch.arange(R, dtype=torch.int32, device=dev)
+        self.row_map = torch.div(self.rows, per_sentence, rounding_mode="floor").to(torch.int32)
+        self.cross_len = self.src_len[self.row_map.long()].to(torch.int32).contiguous()
+
+    def logits(self, tok: torch.Tensor, t: int, anc: Optional[torch.Tensor] = None,
+               want_members: bool = False):
+        """The step at position t on every member: tok int64 [R] -> logits [R, >= V], one
+        member's own or, of several, the log of the weighted mean of their probabilities
+        (`ops.kernels.ensemble_logprobs`). `anc`: the ancestry table of a loop that has one.
+        `want_members`: (those logits, the list of the members' own)."""
+        klen = torch.full((self.R,), t + 1, dtype=torch.int32, device=self.dev)
+        lgs = [st.logits(tok, t, klen, self.cross_len, row_map=self.row_map, anc=anc) for st in self.steps]
+        lg = lgs[0] if len(lgs) == 1 else K.ensemble_logprobs(lgs, self.V, self.weights)
+        return (lg, lgs) if want_members else lg
+
+    def gather(self, parent: torch.Tensor) -> None:
+        """`DecoderStep.gather` on every member."""
+        for st in self.steps:
+            st.gather(parent)

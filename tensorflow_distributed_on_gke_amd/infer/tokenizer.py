@@ -16,6 +16,13 @@ PAD, UNK, START, END = 0, 1, 2, 3
 OFFSET = 4
 
 
+def after_first_end(tokens: torch.Tensor, end: int) -> torch.Tensor:
+    """bool, of tokens' shape [..., L]: the positions strictly after the first `end` along the
+    last dimension. Decoding, scoring and MBR all cut their rows by it."""
+    is_end = (tokens == end).long()
+    return is_end.cumsum(dim=-1) - is_end > 0
+
+
 class ByteTokenizer:
     def __init__(self, vocab_size: int = 260):
         if vocab_size < OFFSET + 256:

@@ -70,7 +70,7 @@ def beam_topk(logits, V: int, score, fin, beam: int, end_id: int, pad_id: int, a
     of beam_topk (csrc/kernels/decode.hip), a wider beam the row / merge pair
     of csrc/kernels/beam_wide.hip, which gives the same bits at any width.
     CPU: the f32 reference of the one-launch kernel, with its bound, 1 <= beam
-    <= 8 (`_beam_topk_torch` is the same definition at any width)."""
+    <= 8 (`beam_topk_torch` is the same definition at any width)."""
     R = logits.shape[0]
     widest = 64 if logits.is_cuda else 8
     if not 1 <= beam <= widest or not 1 <= V <= 65536:
@@ -89,10 +89,10 @@ def beam_topk(logits, V: int, score, fin, beam: int, end_id: int, pad_id: int, a
             C().beam_topk_wide(logits, V, score, fin, beam, end_id, pad_id, score_out, parent, token,
                                fin_out, ws, anc, anc_out, t)
         return score_out, parent, token, fin_out, anc_out
-    return _beam_topk_torch(logits, V, score, fin, beam, end_id, pad_id, anc, t, anc_out)
+    return beam_topk_torch(logits, V, score, fin, beam, end_id, pad_id, anc, t, anc_out)
 
 
-def _beam_topk_torch(logits, V: int, score, fin, beam: int, end_id: int, pad_id: int, anc, t: int, anc_out):
+def beam_topk_torch(logits, V: int, score, fin, beam: int, end_id: int, pad_id: int, anc, t: int, anc_out):
     """The definition of `beam_topk` in torch operations, f32, at any width
     and on any device: its CPU arm, beam search on the CPU above width 8
     (infer/beam.py) and the composition scripts/decode_bench.py times."""
