@@ -777,9 +777,23 @@ struct DsImg {
 // gemm_kernel (3 LDS-DMA stages of 64-deep K tiles, swapped-operand MFMAs,
 // the same k order per element as the standalone NN dgrad, so the bf16 dO is
 // bitwise that kernel's). Uses smem[0, 3 * 24 KiB); returns the accumulators.
+//
+// The attention's own operands (K / V fragments, Q / K / O chunks: FDO_NX HBM
+// reads into registers per lane, every one unconditional) are issued by
+// extra() once the DMA of the LAST stage is out, not in front of the first:
+// loads retire in issue order, so in front they held stage 0 back by the
+// whole 32 MiB read. Behind, no stage waits for them, the last three K steps
+// run under that read (their waits leave its FDO_NX loads in flight), and the
+// 40 registers are not live in the main loop.
 constexpr int FDO_STAGES = 3, FDO_SB = (128 + 64) * BK * 2;
+// FDO_NX must not exceed the vector-memory instructions extra() really emits
+// in every lane (the static_assert at the call counts 16-byte loads in the
+// source): were there fewer, those waits would let a stage be read before it
+// has landed; more (a load the compiler splits) only waits longer.
+constexpr int FDO_NX = 10;
+template <typename Extra>
 __device__ __forceinline__ void fdo_tile(const AttnArgs& a, int b, int h, char* smem, int wid,
-                                         int lane, f32x4 (&acc)[2][2]) {
+                                         int lane, f32x4 (&acc)[2][2], Extra&& extra) {
   constexpr int NW = 8, BM = 128, BN = 64, WN = 2, TM = 2, TN = 2, STAGES = FDO_STAGES;
   constexpr int A_BYTES = BM * BK * 2, SB = FDO_SB;
   using GA = Glds<true, BM, NW>;
@@ -834,8 +848,11 @@ __device__ __forceinline__ void fdo_tile(const AttnArgs& a, int b, int h, char* 
       for (int j = 0; j < TN; ++j) acc[i][j] = mfma16(fb0[j], fa0[i], acc[i][j]);
     prio_lo();
     if constexpr (MODE >= 1) {
-      if constexpr (MODE >= 2) wait_vmcnt<(STAGES - 2) * PT>();
-      else wait_vmcnt<0>();
+      // stage kt + 1 landed; younger: stage kt + 2 (modes 3, 2) and, once
+      // every stage is issued (modes 2, 1), extra()'s loads
+      if constexpr (MODE == 3) wait_vmcnt<(STAGES - 2) * PT>();
+      else if constexpr (MODE == 2) wait_vmcnt<(STAGES - 2) * PT + FDO_NX>();
+      else wait_vmcnt<FDO_NX>();
       lds_barrier();
       const char* nx = smem + ((kt + 1) % STAGES) * SB;
       if constexpr (MODE == 3) {
@@ -861,11 +878,40 @@ __device__ __forceinline__ void fdo_tile(const AttnArgs& a, int b, int h, char* 
   };
   int kt = 0;
   for (; kt + STAGES < nk; ++kt) kstep(kt, std::integral_constant<int, 3>{});
+  asm volatile("" ::: "memory");  // (the issue order is what the waits count)
+  extra();  // every stage is issued
+  asm volatile("" ::: "memory");
   if (kt + STAGES - 1 < nk && kt + 1 < nk) kstep(kt++, std::integral_constant<int, 2>{});
   for (; kt + 1 < nk; ++kt) kstep(kt, std::integral_constant<int, 1>{});
   if (kt < nk) kstep(kt, std::integral_constant<int, 0>{});
   lds_barrier();  // the stages are free for the attention's images
 }
+
+// The fused backward's Q, dO (not FDO: computed in-kernel), O and K tile
+// chunks from global memory into vq / vo / vx / vk (the plain form issues
+// them in its prologue, the FDO form from inside fdo_tile)
+#define TDG_FUSED_BWD_LOAD_CHUNKS()                                                                       \
+  _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                        \
+    const int id = tid + i * NT;                                                                          \
+    const int row = id / CPR, cc = id % CPR;                                                              \
+    vq[i] = vo[i] = vk[i] = vx[i] = z;                                                                    \
+    if constexpr (TOTAL % NT == 0) { /* (clamped rows, zeroed: no branch per load) */                     \
+      const int rq = min(row, a.Lq - 1), rk = min(row, a.Lk - 1);                                         \
+      vq[i] = ld8_or0(qb + (long long)rq * a.q_sl + cc * 8, row < a.Lq);                                  \
+      if constexpr (!FDO) vo[i] = ld8_or0(ob + (long long)rq * a.do_sl + cc * 8, row < a.Lq);             \
+      vx[i] = ld8_or0(obo + (long long)rq * a.o_sl + cc * 8, row < a.Lq);                                 \
+      vk[i] = ld8_or0(kbp + (long long)rk * a.k_sl + cc * 8, row < a.Lk);                                 \
+    } else {                                                                                              \
+      if (id < TOTAL && row < a.Lq) {                                                                     \
+        vq[i] = *reinterpret_cast<const short8_t*>(qb + (long long)row * a.q_sl + cc * 8);                \
+        if constexpr (!FDO)                                                                               \
+          vo[i] = *reinterpret_cast<const short8_t*>(ob + (long long)row * a.do_sl + cc * 8);             \
+        vx[i] = *reinterpret_cast<const short8_t*>(obo + (long long)row * a.o_sl + cc * 8);               \
+      }                                                                                                   \
+      if (id < TOTAL && row < a.Lk)                                                                       \
+        vk[i] = *reinterpret_cast<const short8_t*>(kbp + (long long)row * a.k_sl + cc * 8);               \
+    }                                                                                                     \
+  }
 
 template <int HD, int U, bool FDO = false>
 __global__ __launch_bounds__(512 / U) __attribute__((amdgpu_waves_per_eu(U == 1 ? (HD <= 64 ? 4 : 2) : 2))) void attn_bwd_fused_kernel(AttnArgs a) {
@@ -906,12 +952,14 @@ __global__ __launch_bounds__(512 / U) __attribute__((amdgpu_waves_per_eu(U == 1 
 #pragma unroll
   for (int u = 0; u < U; ++u) key[u] = 16 * (U * w + u) + cl;
   short8_t kf[U][T::KS], vf[U][T::KS];
+  if constexpr (!FDO) {  // (FDO: issued from inside fdo_tile, below)
 #pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const int krow = min(key[u], a.Lk - 1);
-    const bf16_t* kp = kbp + (long long)krow * a.k_sl;
-    const bf16_t* vp = a.v + b * a.v_sb + (long long)krow * a.v_sl + h * a.v_sh;
-    TDG_LOAD_ROW_FRAGS2(HD, lane, key[u] < a.Lk, kf[u], kp, vf[u], vp)
+    for (int u = 0; u < U; ++u) {
+      const int krow = min(key[u], a.Lk - 1);
+      const bf16_t* kp = kbp + (long long)krow * a.k_sl;
+      const bf16_t* vp = a.v + b * a.v_sb + (long long)krow * a.v_sl + h * a.v_sh;
+      TDG_LOAD_ROW_FRAGS2(HD, lane, key[u] < a.Lk, kf[u], kp, vf[u], vp)
+    }
   }
   {
     constexpr int CPR = HD / 8;  // 16-byte chunks per row
@@ -919,34 +967,23 @@ __global__ __launch_bounds__(512 / U) __attribute__((amdgpu_waves_per_eu(U == 1 
     constexpr int NI = (TOTAL + NT - 1) / NT;
     short8_t vq[NI], vo[NI], vk[NI], vx[NI];
     const short8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const int id = tid + i * NT;
-      const int row = id / CPR, cc = id % CPR;
-      vq[i] = vo[i] = vk[i] = vx[i] = z;
-      if constexpr (TOTAL % NT == 0) {  // (clamped rows, zeroed: no branch per load)
-        const int rq = min(row, a.Lq - 1), rk = min(row, a.Lk - 1);
-        vq[i] = ld8_or0(qb + (long long)rq * a.q_sl + cc * 8, row < a.Lq);
-        if constexpr (!FDO) vo[i] = ld8_or0(ob + (long long)rq * a.do_sl + cc * 8, row < a.Lq);
-        vx[i] = ld8_or0(obo + (long long)rq * a.o_sl + cc * 8, row < a.Lq);
-        vk[i] = ld8_or0(kbp + (long long)rk * a.k_sl + cc * 8, row < a.Lk);
-      } else {
-        if (id < TOTAL && row < a.Lq) {
-          vq[i] = *reinterpret_cast<const short8_t*>(qb + (long long)row * a.q_sl + cc * 8);
-          if constexpr (!FDO) vo[i] = *reinterpret_cast<const short8_t*>(ob + (long long)row * a.do_sl + cc * 8);
-          vx[i] = *reinterpret_cast<const short8_t*>(obo + (long long)row * a.o_sl + cc * 8);
-        }
-        if (id < TOTAL && row < a.Lk)
-          vk[i] = *reinterpret_cast<const short8_t*>(kbp + (long long)row * a.k_sl + cc * 8);
-      }
+    if constexpr (!FDO) {
+      TDG_FUSED_BWD_LOAD_CHUNKS()
     }
     const float lse_v = (tid < R && tid < a.Lq) ? a.lse[((long long)b * a.H + h) * a.Lq + tid] : INFINITY;
     if constexpr (FDO) {
-      // dO from the in-kernel output-projection dgrad (rows >= Lq zero, as
-      // the loads above give them), into its image; then read back in the
-      // chunk layout for delta
+      // dO from the in-kernel output-projection dgrad (rows >= Lq zeroed
+      // below, as the chunk loads give theirs), into its image; then read
+      // back in the chunk layout for delta
       f32x4 acc[2][2];
-      fdo_tile(a, b, h, smem, w, lane, acc);
+      static_assert(!FDO || (U * 2 * T::KS + 3 * NI == FDO_NX && TOTAL % NT == 0), "FDO_NX unconditional loads");
+      fdo_tile(a, b, h, smem, w, lane, acc, [&] {
+        const long long krow = min(key[0], a.Lk - 1);
+        TDG_LOAD_ROW_FRAGS2(HD, lane, key[0] < a.Lk, kf[0], kbp + krow * a.k_sl, vf[0],
+                            a.v + b * a.v_sb + krow * a.v_sl + h * a.v_sh)
+        TDG_FUSED_BWD_LOAD_CHUNKS()
+      });
+      TDG_STAMP(5);
       const int wm = w / 2, wn = w % 2;
 #pragma unroll
       for (int i = 0; i < 2; ++i)
@@ -1098,6 +1135,7 @@ __global__ __launch_bounds__(512 / U) __attribute__((amdgpu_waves_per_eu(U == 1 
     TDG_PACK_STORE_ROW(T::DT, lo, hi, dvp, dv[u], 1.f, g, ok)
   }
   __syncthreads();
+  TDG_STAMP(6);
 
   // ---- phase 2: dQ for queries 16 (U w + u) .. +15 (query on lanes)
   if (16 * U * w >= a.Lq) return;
@@ -1128,6 +1166,7 @@ __global__ __launch_bounds__(512 / U) __attribute__((amdgpu_waves_per_eu(U == 1 
 #endif
 }
 
+#undef TDG_FUSED_BWD_LOAD_CHUNKS
 #undef TDG_ATTENDS
 #undef TDG_PDS_KEY_LANE
 #undef TDG_DS_QUERY_LANE

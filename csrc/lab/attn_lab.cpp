@@ -83,6 +83,45 @@ int main() {
     const float tb = lab::graph_us(st, [&] { tdg_attn_bwd(&a, D, st); });
     std::printf("bwd causal=%d %8.2f us | %s\n", causal, tb, sbw.c_str());
     std::fflush(stdout);
+    // backward with the output-projection dgrad in-kernel (FDO), as the
+    // training step runs it: operands and outputs rotate over NSET buffer
+    // sets (64 MiB each, together past the 256 MiB last-level cache), so
+    // every launch reads from HBM
+    constexpr int NSET = 6;
+    static uint16_t* set[NSET][8];  // q k v o dy dq dk dv
+    static uint16_t* wo = nullptr;
+    const int d = H * D;
+    if (!wo) {
+      wo = lab::rand_bf16((size_t)d * d, rng, 0.05f);
+      uint16_t* dy0 = lab::rand_bf16(n, rng, 0.1f);
+      const uint16_t* src[5] = {q, k, v, o, dy0};
+      for (int s = 0; s < NSET; ++s)
+        for (int i = 0; i < 8; ++i) {
+          CK(hipMalloc(&set[s][i], n * 2));
+          if (i < 5) CK(hipMemcpy(set[s][i], src[i], n * 2, hipMemcpyDeviceToDevice));
+        }
+    }
+    int turn = 0;
+    auto fdo = [&] {
+      uint16_t** p = set[turn++ % NSET];
+      AttnArgs f = a;
+      f.q = p[0]; f.k = p[1]; f.v = p[2]; f.o = p[3]; f.dout = nullptr;
+      f.fdo_dy = p[4]; f.fdo_w = wo; f.fdo_d = d; f.fdo_ldy = d; f.fdo_ldw = d;
+      f.dq = p[5]; f.dk = p[6]; f.dv = p[7];
+      f.xcd = 1;
+      CK((hipError_t)tdg_attn_bwd_fdo(&f, st));
+    };
+    for (int i = 0; i < NSET; ++i) fdo();
+    CK(hipStreamSynchronize(st));
+    stamps.clear(st);
+    fdo();
+    CK(hipStreamSynchronize(st));
+    const char* on[6] = {"dO-gemm", "dO+delta+tiles", "phase1", "dS+dKdV-out", "phase2+dQ-out", "drain"};
+    const int oo[7] = {0, 5, 1, 2, 6, 3, 4};
+    const std::string sfo = stamps.summary((size_t)B * H, on, oo, 7);
+    const float tfo = lab::graph_us(st, fdo);
+    std::printf("bwd-fdo causal=%d %8.2f us (HBM-cold rotation) | %s\n", causal, tfo, sfo.c_str());
+    std::fflush(stdout);
   }
   return 0;
 }

@@ -95,22 +95,28 @@ struct Stamps {
   void clear(hipStream_t st) { CK(hipMemsetAsync(d, 0, nblocks * 512 * 8, st)); }
   // "name a b c d" phase summary for phases 0->1->2->3->4 of nwg blocks
   std::string summary(size_t nwg, const char* names[4]) const {
+    const int order[5] = {0, 1, 2, 3, 4};
+    return summary(nwg, names, order, 5);
+  }
+  // the same over the stamp slots order[0] -> order[1] -> ... (n <= 8 slots,
+  // n - 1 names)
+  std::string summary(size_t nwg, const char* const* names, const int* order, int n) const {
     std::vector<unsigned long long> hs(nwg * 512);
     CK(hipMemcpy(hs.data(), d, hs.size() * 8, hipMemcpyDeviceToHost));
-    std::vector<double> ph[4];
+    std::vector<double> ph[7];
     unsigned long long t0min = ~0ull, t0max = 0, t4max = 0;
     for (size_t b = 0; b < nwg; ++b) {
-      unsigned long long t[5];
-      for (int i = 0; i < 5; ++i) t[i] = hs[b * 512 + i * 64];
-      if (!t[0] || !t[4]) continue;
-      for (int i = 0; i < 4; ++i) ph[i].push_back((double)(t[i + 1] - t[i]) * 0.01);
+      unsigned long long t[8];
+      for (int i = 0; i < n; ++i) t[i] = hs[b * 512 + order[i] * 64];
+      if (!t[0] || !t[n - 1]) continue;
+      for (int i = 0; i + 1 < n; ++i) ph[i].push_back((double)(t[i + 1] - t[i]) * 0.01);
       t0min = std::min(t0min, t[0]);
       t0max = std::max(t0max, t[0]);
-      t4max = std::max(t4max, t[4]);
+      t4max = std::max(t4max, t[n - 1]);
     }
-    char buf[512];
+    char buf[768];
     int o = std::snprintf(buf, sizeof(buf), "per-WG median (max) us:");
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i + 1 < n; ++i) {
       std::vector<double> v = ph[i];
       std::sort(v.begin(), v.end());
       const double med = v.empty() ? 0 : v[v.size() / 2], mx = v.empty() ? 0 : v.back();
