@@ -13,6 +13,16 @@ while backward continues):
                     layers as one GEMM (N = layers*2*d)
   EmbedFn         : dropout(emb[tok] * sqrt(d) + PE)
 
+The two attention blocks are one core, _attn_block_fwd / _attn_block_bwd: the
+only place that chooses between the attention kernels (forward: fused
+projection + attention, bf16, e4m3; backward: fused dO, bf16, e5m2-emitting,
+fp8) and that orders the block's weight-gradient, bias-fold and grad-ready
+calls, on GPU and in the CPU reference. The Functions differ in where K, V and
+their gradients live: slots 1 and 2 of the block's own [M, 3d] projection, or
+(_ExtKV) a layer's slice of the batched cross K|V buffers and of KVGrad's; they
+keep their argument lists, the checks and lazy allocations of those buffers,
+and what they hand back to autograd.
+
 Fusions this buys over per-op autograd: the residual gradient is added inside
 the dgrad GEMM epilogue (beta = 1 onto the LayerNorm input gradient) instead
 of an autograd add; the sublayer's output-bias gradient comes out of the
@@ -302,21 +312,22 @@ def attention_probs(q, k, kv_len, causal: bool, scale: float) -> torch.Tensor:
     return _ref_attn_fwd(q, k, k, kv_len, causal, scale)[1]
 
 
-def _attn_out_ln_fwd(ctx, o, s, x, wo: Param, bo: Param, gamma: Param, beta: Param, site: int,
+def _attn_out_ln_fwd(ctx, o, x, wo: Param, bo: Param, gamma: Param, beta: Param, site: int,
                      rt: RunCtx, kx, o8e):
-    """An attention block's forward ending y = LN(x + dropout(o @ Wo^T + bo)) (s: that projection,
-    where the CPU reference computed it); sets ctx.ln and ctx.f8a. kx, o8e: the lean block's
-    kept e4m3 input and the e4m3 O its attention epilogue emitted."""
+    """An attention block's forward ending y = LN(x + dropout(o @ Wo^T + bo)); sets ctx.ln and
+    ctx.f8a. kx, o8e: the lean block's kept e4m3 input and the e4m3 O its attention epilogue
+    emitted."""
     M, d = x.numel() // x.shape[-1], x.shape[-1]
     ctx.f8a = None
     if ctx.lean:  # e4m3 output projection; keep the e4m3 operands for the backward
         s, o8 = rt.fp8.out_proj(o.view(M, d), wo, bo, o8e[0] if o8e else None)
         ctx.f8a = (kx[0], kx[1], o8)
-        y, ctx.ln = _ln_fwd(x, s.view(x.shape), gamma, beta, site, rt)
-    elif s is None:
+    elif x.is_cuda:  # projection fused with the LayerNorm
         y, ctx.ln = _proj_ln_fwd(o.view(M, d), wo, bo, x, gamma, beta, site, rt)
+        return y
     else:
-        y, ctx.ln = _ln_fwd(x, s.view(x.shape), gamma, beta, site, rt)
+        s = o.reshape(M, d) @ wo.master.t() + bo.master
+    y, ctx.ln = _ln_fwd(x, s.view(x.shape), gamma, beta, site, rt)
     return y
 
 
@@ -343,157 +354,208 @@ def _lean_bwd_end(lb: _LeanBwd, g8, w_in: Param, wo: Param, rt: RunCtx) -> None:
     rt.wgrad.add_fp8(g8, st.gmeta.s(lb.gq), lb.x8, st.meta.s(lb.xs), w_in, bt, rt)
 
 
+# =============================================================================== attention block core
+# Cross-attention's K and V lie outside the block, in buffers batched over the decoder layers.
+# Each of kv, kv8, g, g8 is this layer's (K, V) pair of [B, S, H, hd] views (_layer_kv), or
+# (None, None): kv the bf16 K|V, kv8 the e4m3 K|V (scale slot kvs); for the backward g the bf16
+# d(K|V), or g8 the e5m2 d(K|V) in their own gradient slot gk, with their bias-gradient column
+# sums in part ([B, layers * 2d]) at columns cs_k / cs_v.
+_ExtKV = namedtuple("_ExtKV", "kv kv8 kvs g g8 gk part cs_k cs_v",
+                    defaults=((None, None), (None, None), None, None, 0, 0))
+
+
+def _layer_kv(t, layer: int, d: int, heads: int):
+    """Decoder layer `layer`'s (K, V) [B, S, H, hd] views of a batched [B, S, layers * 2d]
+    tensor (the cross K|V or their gradient); (None, None) without one."""
+    if t is None:
+        return None, None
+    B, S = t.shape[:2]
+    return t[:, :, layer * 2 * d:(layer + 1) * 2 * d].view(B, S, 2, heads, d // heads).unbind(2)
+
+
+def _qkv(t, kv, B: int, heads: int, hd: int):
+    """(q, k, v) [B, L, H, hd] views of an input-projection output, or of its gradient, t: the
+    three column slots of t [M, 3d] (self-attention: kv None), or t [M, d] as q and the pair kv
+    from outside the block (cross-attention). t None: None in its places."""
+    if kv is None:
+        return t.view(B, -1, 3, heads, hd).unbind(2) if t is not None else (None, None, None)
+    return (t.view(B, -1, heads, hd) if t is not None else None,) + tuple(kv)
+
+
+def _attn_block_fwd(ctx, x, w_in: Param, b_in: Param, wo: Param, bo: Param, gamma: Param,
+                    beta: Param, heads: int, kv_len, causal: bool, site: int, rt: RunCtx,
+                    ext: Optional[_ExtKV] = None):
+    """Forward of an attention block y = LN(x + dropout(MHA(..) @ Wo^T + bo)), the one place that
+    chooses between the attention forward kernels. Q|K|V = x @ w_in^T + b_in are the column slots
+    of one [M, 3d] projection (self-attention); with `ext` (cross-attention) the projection is Q
+    alone and K, V come from outside. Sets ctx.p, meta, lean, f8b (the fp8 backward is planned),
+    q8 (the e4m3 projection output and its scale slot, where the e4m3 attention read it) and
+    what _attn_out_ln_fwd sets. Returns (y, x2, proj, o, aux); proj None: only its e4m3 copy
+    was written."""
+    B, L, d = x.shape
+    hd = d // heads
+    scale = 1.0 / math.sqrt(hd)
+    ctx.p = (w_in, b_in, wo, bo, gamma, beta)
+    ctx.meta = (heads, causal, scale, site, rt)
+    x2 = x.reshape(B * L, d)
+    ctx.lean = lean = x.is_cuda and _attn_lean(rt, B * L, w_in, wo, d)
+    kx = [] if lean else None
+    ctx.q8 = o8e = None
+    kv, kv8 = (ext.kv, ext.kv8) if ext is not None else (None, None)
+    if x.is_cuda:
+        Lk = L if ext is None else (kv8 if kv[0] is None else kv)[0].shape[1]
+        f8 = (rt.fp8 is not None and (ext is None or kv8[0] is not None)
+              and K.attn_fwd_fp8_ok(L, Lk, hd))
+        # the fp8 backward reads only the e4m3 Q|K|V: no bf16 copy then
+        ctx.f8b = f8b = f8 and _f8_bwd_planned(rt, lean, L, Lk, hd)
+        if ext is not None and kv[0] is None and not f8b:
+            raise RuntimeError("cross-attention: the batched K|V were produced for the fp8 "
+                               "backward (no bf16 copy) but this layer does not run it")
+        r = (rt.fp8.linear(x2, w_in, b_in, want8=f8, keep_x8=kx, want_y=not f8b)
+             if rt.fp8 is not None else None)
+        proj, proj8 = (r[0], r[1]) if f8 and r is not None else (r, None)
+        fused = None
+        if proj is None and not f8b and rt.fp8 is None and rt.attn_maps is None:
+            # projection + attention forward in one launch (<= 128 tokens)
+            fused = K.qkv_attn_fwd(x2, w_in.compute, b_in.master, B, heads, kv_len, scale, causal,
+                                   *(kv or ()))
+            if fused is not None:
+                proj = fused[0]
+        if proj is None and not f8b:
+            proj = K.linear_fwd(x2, w_in.compute, b_in.master)  # [M, 3d] / [M, d]
+        q, k, v = _qkv(proj, kv, B, heads, hd)
+        if fused is not None:
+            o, aux = fused[1], fused[2]
+        elif proj8 is not None:  # e4m3 attention on the projection's e4m3 output (and, for
+            # cross-attention, the batched e4m3 K|V)
+            sq = rt.fp8.meta.s(r[2])
+            skv = sq if ext is None else rt.fp8.meta.s(ext.kvs)
+            ctx.q8 = (proj8, r[2])  # (the fp8 attention backward's operands)
+            # (lean: the epilogue also emits the e4m3 O of the output projection)
+            o8e = rt.fp8.o8_for(wo, (B, L, heads, hd), x.device) if lean else None
+            o, aux = K.attn_fwd_fp8(*_qkv(proj8, kv8, B, heads, hd), sq, skv, skv, kv_len, scale,
+                                    causal, *(o8e or ()))
+        else:
+            o, aux = K.attn_fwd(q, k, v, kv_len, scale, causal)
+    else:
+        proj = x2 @ w_in.master.t() + b_in.master
+        q, k, v = _qkv(proj, kv, B, heads, hd)
+        o, aux = _ref_attn_fwd(q, k, v, kv_len, causal, scale)
+    if rt.attn_maps is not None:  # (_f8_bwd_planned: the bf16 q, k exist when maps are asked for)
+        rt.attn_maps[site] = attention_probs(q, k, kv_len, causal, scale)
+    y = _attn_out_ln_fwd(ctx, o, x, wo, bo, gamma, beta, site, rt, kx, o8e)
+    return y, x2, proj, o, aux
+
+
+def _attn_block_bwd(ctx, dy, x2, proj, o, aux, kv_len, ext: Optional[_ExtKV] = None):
+    """Backward of _attn_block_fwd -> dx [B, L, d], the one place that chooses between the
+    attention backward kernels. Writes the block's parameter gradients and, with `ext`, this
+    layer's d(K|V) into ext.g / ext.g8. Lean fp8 blocks: e5m2 ds from the LayerNorm backward ->
+    O-proj dgrad (e5m2 x e4m3 Wo^T) -> attention backward -> e5m2 dQ|dK|dV -> input-projection
+    dgrad (into the residual gradient); both weight gradients in fp8 from the saved e4m3
+    operands."""
+    w_in, b_in, wo, bo, gamma, beta = ctx.p
+    heads, causal, scale, site, rt = ctx.meta
+    B, L, d = dy.shape
+    M, hd, N = B * L, d // heads, w_in.shape[0]
+    kv, kv8, gkv, gkv8 = (ext.kv, ext.kv8, ext.g, ext.g8) if ext is not None else (None,) * 4
+    cs_k, cs_v = (ext.cs_k, ext.cs_v) if ext is not None else (d, 2 * d)
+    tag = f"{'qkv' if ext is None else 'q'}{site}"  # (workspaces: one per site and purpose)
+    q, k, v = _qkv(proj, kv, B, heads, hd)
+    if ctx.lean:
+        st = rt.fp8
+        lb = _lean_bwd_begin(ctx, dy, w_in, site, rt)
+        sg, ag = st.gmeta.s(lb.gq), st.gmeta.a(lb.gq)
+        if ctx.f8b and ctx.q8 is not None:  # (planned by the forward, which kept the e4m3 operands)
+            # fp8 attention backward: e5m2 dO straight from the output projection's dgrad, e4m3
+            # Q/K/V of the forward -> e5m2 dQ|dK|dV (+ amax, bias sums). Cross-attention: dK / dV
+            # as e5m2 straight into the batched buffer (the cross K|V projection's gradient
+            # slot, bias sums into its own part), or bf16 into the batched cross K|V gradient
+            gdo, gds = st.attn_bwd8[id(wo)]
+            do8 = _fp8_dgrad(lb.ds8, lb.go, wo, None, rt, out8_slot=gdo)
+            proj8, qs = ctx.q8
+            sq = st.meta.s(qs)
+            skv = sq if ext is None else st.meta.s(ext.kvs)
+            g8 = torch.empty(M, N, dtype=st.gmeta.dtype, device=dy.device)
+            dq8, dk8, dv8 = _qkv(g8, gkv8, B, heads, hd)
+            dk, dv = gkv or (None, None)
+            part = K.workspace(f"f8cs_{tag}", B * N, dy.device)
+            own = {}
+            if ext is not None and ext.part is not None:
+                own = dict(sgkv8=st.gmeta.s(ext.gk), amaxgkv8=st.gmeta.a(ext.gk),
+                           cs_part2=ext.part, cs_ld2=ext.part.shape[1])
+            nparts = K.attn_bwd_f8(*_qkv(proj8, kv8, B, heads, hd), sq, skv, skv, o,
+                                   do8.view(B, L, heads, hd), st.gmeta.s(gdo), aux, kv_len, scale,
+                                   causal, st.gmeta.s(gds), st.gmeta.a(gds), dk=dk, dv=dv, dq8=dq8,
+                                   dk8=dk8, dv8=dv8, sg8=sg, amaxg8=ag, cs_part=part, cs_ld=N,
+                                   cs_q=0, cs_k=cs_k, cs_v=cs_v, **own)
+            _fold_bias_later(rt, part[: nparts * N], nparts, N, b_in)
+        else:
+            do = torch.empty(M, d, dtype=torch.bfloat16, device=dy.device)
+            _fp8_dgrad(lb.ds8, lb.go, wo, do, rt, 0.0)
+            g = torch.empty(M, N, dtype=torch.bfloat16, device=dy.device)
+            dq, dk, dv = _qkv(g, gkv, B, heads, hd)
+            if fp8.ATTN_BWD_G8 and K.attn_bwd_g8_ok(L, k.shape[1], hd):
+                # the attention backward emits e5m2 dQ|dK|dV, their amax and the bias-gradient
+                # partials itself (no bf16 dQ|dK|dV pass). Cross-attention: of dQ alone; dK / dV
+                # stay bf16 (summed over the layers into the batched cross K|V gradient), so
+                # the bf16 writes are not skipped
+                g8 = torch.empty(M, N, dtype=st.gmeta.dtype, device=dy.device)
+                dq8, dk8, dv8 = _qkv(g8, gkv8, B, heads, hd)
+                part = K.workspace(f"qcs_{tag}", B * -(-L // 128) * N, dy.device)
+                nparts = K.attn_bwd_g8(q, k, v, o, do.view(B, L, heads, hd), aux, dq, dk, dv,
+                                       kv_len, scale, causal, dq8, dk8, dv8, sg, ag, part, N, 0,
+                                       cs_k, cs_v, skip_bf16=ext is None)
+                _fold_bias_later(rt, part[: nparts * N], nparts, N, b_in)
+            else:
+                K.attn_bwd(q, k, v, o, do.view(B, L, heads, hd), aux, dq, dk, dv, kv_len, scale,
+                           causal)
+                g8 = _fp8_grad_bias(g, lb.gq, b_in, rt, tag)
+        _lean_bwd_end(lb, g8, w_in, wo, rt)
+        return lb.dh.view(B, L, d)
+    dh, ds = _ln_bwd(dy, ctx.ln, gamma, beta, bo, site, rt)
+    ds2 = ds.reshape(M, d)
+    if dy.is_cuda:
+        _wgrad(rt, ds2, o.view(M, d), d, wo)
+        g = torch.empty(M, N, dtype=torch.bfloat16, device=dy.device)
+        dq, dk, dv = _qkv(g, gkv, B, heads, hd)
+        # (<= 128 tokens: the output projection's dgrad dO = ds @ Wo inside the attention
+        # backward)
+        if not K.attn_bwd_fdo(q, k, v, o, ds2, wo.compute, aux, dq, dk, dv, kv_len, scale, causal):
+            do = K.linear_dgrad(ds2, wo.compute, d)
+            K.attn_bwd(q, k, v, o, do.view(B, L, heads, hd), aux, dq, dk, dv, kv_len, scale, causal)
+        _wgrad(rt, g, x2, N, w_in, b_in)
+    else:
+        _write_grad(wo, ds2.t() @ o.reshape(M, d), rt)
+        _ready(rt, wo)
+        do = (ds2 @ wo.master).view(B, L, heads, hd)
+        g = torch.empty(M, N, dtype=ds2.dtype)
+        for dst, src in zip(_qkv(g, gkv, B, heads, hd), _ref_attn_bwd(q, k, v, aux, do, scale)):
+            dst.copy_(src)
+        _write_grad(w_in, g.t() @ x2, rt)
+        _write_grad(b_in, g.sum(0), rt)
+        _ready(rt, w_in, b_in)  # (GPU: reported by _wgrad / the deferred flush)
+    return _dgrad_into(g, w_in, N, dh).view(B, L, d)
+
+
 # =============================================================================== self-attention block
 class SelfAttnBlockFn(torch.autograd.Function):
     NO_GRAD_ARGS = 11  # forward arguments after x
     @staticmethod
     def forward(ctx, x, wqkv: Param, bqkv: Param, wo: Param, bo: Param, gamma: Param,
                 beta: Param, heads: int, kv_len, causal: bool, site: int, rt: RunCtx):
-        B, L, d = x.shape
-        hd = d // heads
-        scale = 1.0 / math.sqrt(hd)
-        ctx.p = (wqkv, bqkv, wo, bo, gamma, beta)
-        ctx.meta = (heads, causal, scale, site, rt)
-        x2 = x.reshape(B * L, d)
-        ctx.lean = lean = x.is_cuda and _attn_lean(rt, B * L, wqkv, wo, d)
-        kx = [] if lean else None
-        o8e = None
-        if x.is_cuda:
-            f8 = rt.fp8 is not None and K.attn_fwd_fp8_ok(L, L, hd)
-            # the fp8 backward reads only the e4m3 Q|K|V: no bf16 copy then
-            ctx.f8b = f8 and _f8_bwd_planned(rt, lean, L, L, hd)
-            r = (rt.fp8.linear(x2, wqkv, bqkv, want8=f8, keep_x8=kx, want_y=not ctx.f8b)
-                 if rt.fp8 is not None else None)
-            qkv, qkv8 = (r[0], r[1]) if f8 and r is not None else (r, None)
-            fused = None
-            if qkv is None and not ctx.f8b and rt.fp8 is None and rt.attn_maps is None:
-                # projection + attention forward in one launch (L <= 128)
-                fused = K.qkv_attn_fwd(x2, wqkv.compute, bqkv.master, B, heads, kv_len, scale, causal)
-                if fused is not None:
-                    qkv = fused[0]
-            if qkv is None and not ctx.f8b:
-                qkv = K.linear_fwd(x2, wqkv.compute, bqkv.master)  # [M, 3d]
-            q5 = qkv.view(B, L, 3, heads, hd) if qkv is not None else None
-            ctx.q8 = None
-            if fused is not None:
-                o, aux = fused[1], fused[2]
-            elif qkv8 is not None:  # e4m3 attention on the projection's e4m3 output
-                q85 = qkv8.view(B, L, 3, heads, hd)
-                s8 = rt.fp8.meta.s(r[2])
-                ctx.q8 = (qkv8, r[2])  # (the fp8 attention backward's operands)
-                # (lean: the epilogue also emits the e4m3 O of the output projection)
-                o8e = rt.fp8.o8_for(wo, (B, L, heads, hd), x.device) if lean else None
-                o, aux = K.attn_fwd_fp8(q85[:, :, 0], q85[:, :, 1], q85[:, :, 2], s8, s8, s8, kv_len,
-                                        scale, causal, *(o8e or ()))
-            else:
-                o, aux = K.attn_fwd(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], kv_len, scale, causal)
-            s = None  # projection fused with the LayerNorm below
-        else:
-            qkv = x2 @ wqkv.master.t() + bqkv.master
-            q5 = qkv.view(B, L, 3, heads, hd)
-            o, aux = _ref_attn_fwd(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], kv_len, causal, scale)
-            s = o.reshape(B * L, d) @ wo.master.t() + bo.master
-        if rt.attn_maps is not None:  # (_f8_bwd_planned: q5 exists when maps are asked for)
-            rt.attn_maps[site] = attention_probs(q5[:, :, 0], q5[:, :, 1], kv_len, causal, scale)
-        y = _attn_out_ln_fwd(ctx, o, s, x, wo, bo, gamma, beta, site, rt, kx, o8e)
+        y, x2, qkv, o, aux = _attn_block_fwd(ctx, x, wqkv, bqkv, wo, bo, gamma, beta, heads, kv_len,
+                                             causal, site, rt)
         ctx.save_for_backward(x2, qkv, o, aux, kv_len)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        if ctx.lean:
-            return SelfAttnBlockFn._backward_fp8(ctx, dy)
-        wqkv, bqkv, wo, bo, gamma, beta = ctx.p
-        heads, causal, scale, site, rt = ctx.meta
-        x2, qkv, o, aux, kv_len = ctx.saved_tensors
-        B, L, d = dy.shape
-        M, hd = B * L, d // heads
-        dh, ds = _ln_bwd(dy, ctx.ln, gamma, beta, bo, site, rt)
-        ds2 = ds.reshape(M, d)
-        q5 = qkv.view(B, L, 3, heads, hd)
-        if dy.is_cuda:
-            _wgrad(rt, ds2, o.view(M, d), d, wo)
-            dqkv = torch.empty(M, 3 * d, dtype=torch.bfloat16, device=dy.device)
-            g5 = dqkv.view(B, L, 3, heads, hd)
-            # (L <= 128: the output projection's dgrad dO = ds @ Wo inside the
-            # attention backward)
-            if not K.attn_bwd_fdo(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], o, ds2, wo.compute, aux,
-                                  g5[:, :, 0], g5[:, :, 1], g5[:, :, 2], kv_len, scale, causal):
-                do = K.linear_dgrad(ds2, wo.compute, d)
-                K.attn_bwd(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], o, do.view(B, L, heads, hd), aux,
-                           g5[:, :, 0], g5[:, :, 1], g5[:, :, 2], kv_len, scale, causal)
-            _wgrad(rt, dqkv, x2, 3 * d, wqkv, bqkv)
-        else:
-            _write_grad(wo, ds2.t() @ o.reshape(M, d), rt)
-            _ready(rt, wo)
-            do = (ds2 @ wo.master).view(B, L, heads, hd)
-            dq, dk, dv = _ref_attn_bwd(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], aux, do, scale)
-            dqkv = torch.stack([dq, dk, dv], dim=2).reshape(M, 3 * d)
-            _write_grad(wqkv, dqkv.t() @ x2, rt)
-            _write_grad(bqkv, dqkv.sum(0), rt)
-            _ready(rt, wqkv, bqkv)  # (GPU: reported by _wgrad / the deferred flush)
-        dx = _dgrad_into(dqkv, wqkv, 3 * d, dh)
+        dx = _attn_block_bwd(ctx, dy, *ctx.saved_tensors)
+        rt = ctx.meta[-1]
         if dy.is_cuda and rt.wgrad is not None:
             rt.wgrad.layer_end()  # self-attention is a layer's first block
-        return (dx.view(B, L, d),) + (None,) * SelfAttnBlockFn.NO_GRAD_ARGS
-
-    @staticmethod
-    def _backward_fp8(ctx, dy):
-        """Lean fp8 backward: e5m2 ds from the LayerNorm backward -> O-proj
-        dgrad (e5m2 x e4m3 Wo^T) -> bf16 attention backward -> e5m2 dQ|dK|dV
-        -> input-projection dgrad (into the residual gradient); both weight
-        gradients in fp8 from the saved e4m3 operands."""
-        wqkv, bqkv, wo = ctx.p[:3]
-        heads, causal, scale, site, rt = ctx.meta
-        x2, qkv, o, aux, kv_len = ctx.saved_tensors
-        B, L, d = dy.shape
-        M, hd = B * L, d // heads
-        st = rt.fp8
-        lb = _lean_bwd_begin(ctx, dy, wqkv, site, rt)
-        ds8, go, gq = lb.ds8, lb.go, lb.gq
-        if ctx.f8b and ctx.q8 is not None:  # (planned by the forward, which kept the e4m3 operands)
-            # fp8 attention backward: e5m2 dO straight from the output
-            # projection's dgrad, e4m3 Q/K/V of the forward -> e5m2 dQ|dK|dV
-            gdo, gds = st.attn_bwd8[id(wo)]
-            do8 = _fp8_dgrad(ds8, go, wo, None, rt, out8_slot=gdo)
-            qkv8, qs = ctx.q8
-            q85 = qkv8.view(B, L, 3, heads, hd)
-            s8 = st.meta.s(qs)
-            dqkv8 = torch.empty(M, 3 * d, dtype=st.gmeta.dtype, device=dy.device)
-            g85 = dqkv8.view(B, L, 3, heads, hd)
-            part = K.workspace(f"f8cs_qkv{site}", B * 3 * d, dy.device)
-            nparts = K.attn_bwd_f8(q85[:, :, 0], q85[:, :, 1], q85[:, :, 2], s8, s8, s8, o,
-                                   do8.view(B, L, heads, hd), st.gmeta.s(gdo), aux, kv_len, scale,
-                                   causal, st.gmeta.s(gds), st.gmeta.a(gds), dq8=g85[:, :, 0],
-                                   dk8=g85[:, :, 1], dv8=g85[:, :, 2], sg8=st.gmeta.s(gq),
-                                   amaxg8=st.gmeta.a(gq), cs_part=part, cs_ld=3 * d, cs_q=0,
-                                   cs_k=d, cs_v=2 * d)
-            _fold_bias_later(rt, part[: nparts * 3 * d], nparts, 3 * d, bqkv)
-        else:
-            do = torch.empty(M, d, dtype=torch.bfloat16, device=dy.device)
-            _fp8_dgrad(ds8, go, wo, do, rt, 0.0)
-            q5 = qkv.view(B, L, 3, heads, hd)
-            dqkv = torch.empty(M, 3 * d, dtype=torch.bfloat16, device=dy.device)
-            g5 = dqkv.view(B, L, 3, heads, hd)
-            if fp8.ATTN_BWD_G8 and K.attn_bwd_g8_ok(L, L, hd):
-                # the attention backward emits e5m2 dQ|dK|dV, their amax and the
-                # bias-gradient partials itself (no bf16 dQ|dK|dV pass)
-                dqkv8 = torch.empty(M, 3 * d, dtype=st.gmeta.dtype, device=dy.device)
-                g85 = dqkv8.view(B, L, 3, heads, hd)
-                part = K.workspace(f"qcs_qkv{site}", B * -(-L // 128) * 3 * d, dy.device)
-                nparts = K.attn_bwd_g8(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], o,
-                                       do.view(B, L, heads, hd), aux, g5[:, :, 0], g5[:, :, 1],
-                                       g5[:, :, 2], kv_len, scale, causal, g85[:, :, 0], g85[:, :, 1],
-                                       g85[:, :, 2], st.gmeta.s(gq), st.gmeta.a(gq), part, 3 * d, 0, d,
-                                       2 * d)
-                _fold_bias_later(rt, part[: nparts * 3 * d], nparts, 3 * d, bqkv)
-            else:
-                K.attn_bwd(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], o, do.view(B, L, heads, hd), aux,
-                           g5[:, :, 0], g5[:, :, 1], g5[:, :, 2], kv_len, scale, causal)
-                dqkv8 = _fp8_grad_bias(dqkv, gq, bqkv, rt, f"qkv{site}")
-        _lean_bwd_end(lb, dqkv8, wqkv, wo, rt)
-        rt.wgrad.layer_end()  # self-attention is a layer's first block
-        return (lb.dh.view(B, L, d),) + (None,) * SelfAttnBlockFn.NO_GRAD_ARGS
+        return (dx,) + (None,) * SelfAttnBlockFn.NO_GRAD_ARGS
 
 
 # =============================================================================== cross-attention
@@ -602,179 +664,57 @@ class CrossAttnBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, kv_all, layer: int, kvh: KVGrad, wq: Param, bq: Param, wo: Param,
                 bo: Param, gamma: Param, beta: Param, heads: int, kv_len, site: int, rt: RunCtx):
-        B, T, d = x.shape
-        S = kv_all.shape[1]
-        hd = d // heads
-        scale = 1.0 / math.sqrt(hd)
-        ctx.p = (wq, bq, wo, bo, gamma, beta)
-        ctx.meta = (heads, scale, site, rt, layer, kvh)
-        x2 = x.reshape(B * T, d)
-        kv5 = None  # (kvh.f8b: kv_all is a placeholder, the e4m3 K|V are read)
-        if not kvh.f8b:
-            if not kv_all.is_contiguous():
-                raise ValueError("kv_all must be contiguous")
-            kv5 = kv_all[:, :, layer * 2 * d:(layer + 1) * 2 * d].view(B, S, 2, heads, hd)
-        ctx.lean = lean = x.is_cuda and _attn_lean(rt, B * T, wq, wo, d)
-        kx = [] if lean else None
-        o8e = None
-        if x.is_cuda:
-            f8 = (rt.fp8 is not None and rt.fp8.kv8 is not None and K.attn_fwd_fp8_ok(T, S, hd))
-            ctx.f8b = f8 and _f8_bwd_planned(rt, lean, T, S, hd)
-            if kvh.f8b and not ctx.f8b:
-                raise RuntimeError("cross-attention: the batched K|V were produced for the fp8 "
-                                   "backward (no bf16 copy) but this layer does not run it")
-            r = (rt.fp8.linear(x2, wq, bq, want8=f8, keep_x8=kx, want_y=not ctx.f8b)
-                 if rt.fp8 is not None else None)
-            q, q8 = (r[0], r[1]) if f8 and r is not None else (r, None)
-            fused = None
-            if q is None and not ctx.f8b and rt.fp8 is None and rt.attn_maps is None and kv5 is not None:
-                # Q projection + attention forward in one launch (<= 128 tokens)
-                fused = K.qkv_attn_fwd(x2, wq.compute, bq.master, B, heads, kv_len, scale, False,
-                                       k=kv5[:, :, 0], v=kv5[:, :, 1])
-                if fused is not None:
-                    q = fused[0]
-            if q is None and not ctx.f8b:
-                q = K.linear_fwd(x2, wq.compute, bq.master)
-            ctx.q8 = None
-            if fused is not None:
-                o, aux = fused[1], fused[2]
-            elif q8 is not None:  # e4m3 attention: e4m3 Q and the batched e4m3 K|V
-                kv8, kvs = rt.fp8.kv8
-                if kv8.shape != kv_all.shape:
-                    raise RuntimeError(f"fp8 cross K|V {tuple(kv8.shape)} is not this forward's "
-                                       f"{tuple(kv_all.shape)}")
-                kv85 = kv8[:, :, layer * 2 * d:(layer + 1) * 2 * d].view(B, S, 2, heads, hd)
-                skv = rt.fp8.meta.s(kvs)
-                ctx.q8 = (q8, r[2], kv85, kvs)  # (the fp8 attention backward's operands)
-                o8e = rt.fp8.o8_for(wo, (B, T, heads, hd), x.device) if lean else None
-                o, aux = K.attn_fwd_fp8(q8.view(B, T, heads, hd), kv85[:, :, 0], kv85[:, :, 1],
-                                        rt.fp8.meta.s(r[2]), skv, skv, kv_len, scale, False,
-                                        *(o8e or ()))
-            else:
-                o, aux = K.attn_fwd(q.view(B, T, heads, hd), kv5[:, :, 0], kv5[:, :, 1], kv_len,
-                                    scale, False)
-            s = None  # projection fused with the LayerNorm below
-        else:
-            q = x2 @ wq.master.t() + bq.master
-            o, aux = _ref_attn_fwd(q.view(B, T, heads, hd), kv5[:, :, 0], kv5[:, :, 1], kv_len,
-                                   False, scale)
-            s = o.reshape(B * T, d) @ wo.master.t() + bo.master
-        if rt.attn_maps is not None:  # (_f8_bwd_planned: q exists when maps are asked for)
-            rt.attn_maps[site] = attention_probs(q.view(B, T, heads, hd), kv5[:, :, 0], kv_len, False, scale)
-        y = _attn_out_ln_fwd(ctx, o, s, x, wo, bo, gamma, beta, site, rt, kx, o8e)
+        d = x.shape[-1]
+        # (kvh.f8b: kv_all is a placeholder, the e4m3 K|V are read)
+        if not kvh.f8b and not kv_all.is_contiguous():
+            raise ValueError("kv_all must be contiguous")
+        kv8, kvs = (None, None), None
+        if x.is_cuda and rt.fp8 is not None and rt.fp8.kv8 is not None:
+            t8, kvs = rt.fp8.kv8  # the batched e4m3 K|V
+            if t8.shape != kv_all.shape:
+                raise RuntimeError(f"fp8 cross K|V {tuple(t8.shape)} is not this forward's "
+                                   f"{tuple(kv_all.shape)}")
+            kv8 = _layer_kv(t8, layer, d, heads)
+        ext = _ExtKV(_layer_kv(None if kvh.f8b else kv_all, layer, d, heads), kv8, kvs)
+        y, x2, q, o, aux = _attn_block_fwd(ctx, x, wq, bq, wo, bo, gamma, beta, heads, kv_len, False,
+                                           site, rt, ext)
+        ctx.layer, ctx.kvh = layer, kvh
+        # (kept for the fp8 attention backward, with ctx.q8, only where the e4m3 attention ran)
+        ctx.kv8 = (kv8, kvs) if ctx.q8 is not None else ((None, None), None)
         ctx.save_for_backward(x2, kv_all, q, o, aux, kv_len)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        wq, bq, wo, bo, gamma, beta = ctx.p
-        heads, scale, site, rt, layer, kvh = ctx.meta
+        heads, rt = ctx.meta[0], ctx.meta[-1]
+        layer, kvh = ctx.layer, ctx.kvh
         x2, kv_all, q, o, aux, kv_len = ctx.saved_tensors
-        B, T, d = dy.shape
-        S = kv_all.shape[1]
-        M, hd = B * T, d // heads
+        B, S, NKV = kv_all.shape
+        d = dy.shape[-1]
+        kv = dkv_all = gk = None
+        cs_k = cs_v = 0
         if kvh.f8b:
-            # every layer's d(K|V) goes to kvh.buf8 as e5m2: autograd gets a
-            # zero-stride placeholder of the right shape, no bf16 buffer
-            dkv_all = kv5 = g5 = None
+            # every layer's d(K|V) goes to kvh.buf8 as e5m2 (the cross K|V projection's
+            # gradient slot), their bias sums to kvh.part: no bf16 buffer
+            if kvh.buf8 is None:
+                kvh.buf8 = torch.empty(B, S, NKV, dtype=rt.fp8.gmeta.dtype, device=dy.device)
+                kvh.part = torch.empty(B, NKV, dtype=torch.float32, device=dy.device)
+            gk = rt.fp8.proj_bwd[id(kvh.wkv)]
+            cs_k, cs_v = layer * 2 * d, layer * 2 * d + d
         else:
             if kvh.buf is None:
-                kvh.buf = torch.empty(B * S, kv_all.shape[2], dtype=kv_all.dtype, device=dy.device)
-            dkv_all = kvh.buf.view(B, S, -1)
-            kv5 = kv_all[:, :, layer * 2 * d:(layer + 1) * 2 * d].view(B, S, 2, heads, hd)
-            g5 = dkv_all[:, :, layer * 2 * d:(layer + 1) * 2 * d].view(B, S, 2, heads, hd)
-        if ctx.lean:
-            st = rt.fp8
-            lb = _lean_bwd_begin(ctx, dy, wq, site, rt)
-            dh, ds8, go, gq = lb.dh, lb.ds8, lb.go, lb.gq
-            if ctx.f8b and ctx.q8 is not None:  # (planned by the forward, which kept the e4m3 operands)
-                # fp8 attention backward: e5m2 dQ (+ amax, bias sums); dK / dV
-                # as e5m2 into kvh.buf8 (kvh.f8b) or bf16 into the batched
-                # cross K|V gradient
-                gdo, gds = st.attn_bwd8[id(wo)]
-                do8 = _fp8_dgrad(ds8, go, wo, None, rt, out8_slot=gdo)
-                q8, qs, kv85, kvs = ctx.q8
-                skv = st.meta.s(kvs)
-                dq8 = torch.empty(M, d, dtype=st.gmeta.dtype, device=dy.device)
-                part = K.workspace(f"f8cs_q{site}", B * d, dy.device)
-                if kvh.f8b:
-                    # e5m2 d(K|V) straight into the batched buffer (the cross K|V
-                    # projection's gradient slot), bias sums into kvh.part
-                    NKV = kv_all.shape[2]
-                    if kvh.buf8 is None:
-                        kvh.buf8 = torch.empty(B, S, NKV, dtype=st.gmeta.dtype, device=dy.device)
-                        kvh.part = torch.empty(B, NKV, dtype=torch.float32, device=dy.device)
-                    g85 = kvh.buf8[:, :, layer * 2 * d:(layer + 1) * 2 * d].view(B, S, 2, heads, hd)
-                    gk = st.proj_bwd[id(kvh.wkv)]
-                    kvo = dict(dk8=g85[:, :, 0], dv8=g85[:, :, 1], sgkv8=st.gmeta.s(gk),
-                               amaxgkv8=st.gmeta.a(gk), cs_part2=kvh.part, cs_ld2=NKV,
-                               cs_k=layer * 2 * d, cs_v=layer * 2 * d + d)
-                else:
-                    kvo = dict(dk=g5[:, :, 0], dv=g5[:, :, 1])
-                nparts = K.attn_bwd_f8(q8.view(B, T, heads, hd), kv85[:, :, 0], kv85[:, :, 1],
-                                       st.meta.s(qs), skv, skv, o, do8.view(B, T, heads, hd),
-                                       st.gmeta.s(gdo), aux, kv_len, scale, False, st.gmeta.s(gds),
-                                       st.gmeta.a(gds), dq8=dq8.view(B, T, heads, hd),
-                                       sg8=st.gmeta.s(gq), amaxg8=st.gmeta.a(gq), cs_part=part,
-                                       cs_ld=d, cs_q=0, **kvo)
-                _fold_bias_later(rt, part[: nparts * d], nparts, d, bq)
-            else:
-                do = torch.empty(M, d, dtype=torch.bfloat16, device=dy.device)
-                _fp8_dgrad(ds8, go, wo, do, rt, 0.0)
-                dq = torch.empty(M, d, dtype=torch.bfloat16, device=dy.device)
-                if fp8.ATTN_BWD_G8 and K.attn_bwd_g8_ok(T, S, hd):
-                    # e5m2 dQ (+ amax, bias partials) from the attention backward;
-                    # dK / dV stay bf16 (summed over the layers into the batched
-                    # cross K|V gradient)
-                    dq8 = torch.empty(M, d, dtype=st.gmeta.dtype, device=dy.device)
-                    part = K.workspace(f"qcs_q{site}", B * -(-T // 128) * d, dy.device)
-                    nparts = K.attn_bwd_g8(q.view(B, T, heads, hd), kv5[:, :, 0], kv5[:, :, 1], o,
-                                           do.view(B, T, heads, hd), aux, dq.view(B, T, heads, hd),
-                                           g5[:, :, 0], g5[:, :, 1], kv_len, scale, False,
-                                           dq8.view(B, T, heads, hd), None, None, st.gmeta.s(gq),
-                                           st.gmeta.a(gq), part, d, 0, 0, 0, skip_bf16=False)
-                    _fold_bias_later(rt, part[: nparts * d], nparts, d, bq)
-                else:
-                    K.attn_bwd(q.view(B, T, heads, hd), kv5[:, :, 0], kv5[:, :, 1], o,
-                               do.view(B, T, heads, hd), aux, dq.view(B, T, heads, hd), g5[:, :, 0],
-                               g5[:, :, 1], kv_len, scale, False)
-                    dq8 = _fp8_grad_bias(dq, gq, bq, rt, f"q{site}")
-            _lean_bwd_end(lb, dq8, wq, wo, rt)
-            dkv_ret = None
-            if layer == 0:  # (kvh.f8b: the zero-stride placeholder)
-                dkv_ret = dkv_all if dkv_all is not None else torch.zeros(
-                    1, dtype=kv_all.dtype, device=dy.device).expand(kv_all.shape)
-            return (dh.view(B, T, d), dkv_ret) + (None,) * CrossAttnBlockFn.NO_GRAD_ARGS
-        dh, ds = _ln_bwd(dy, ctx.ln, gamma, beta, bo, site, rt)
-        ds2 = ds.reshape(M, d)
-        if dy.is_cuda:
-            _wgrad(rt, ds2, o.view(M, d), d, wo)
-            dq = torch.empty(M, d, dtype=torch.bfloat16, device=dy.device)
-            if not K.attn_bwd_fdo(q.view(B, T, heads, hd), kv5[:, :, 0], kv5[:, :, 1], o, ds2,
-                                  wo.compute, aux, dq.view(B, T, heads, hd), g5[:, :, 0],
-                                  g5[:, :, 1], kv_len, scale, False):
-                do = K.linear_dgrad(ds2, wo.compute, d)
-                K.attn_bwd(q.view(B, T, heads, hd), kv5[:, :, 0], kv5[:, :, 1], o,
-                           do.view(B, T, heads, hd), aux, dq.view(B, T, heads, hd), g5[:, :, 0],
-                           g5[:, :, 1], kv_len, scale, False)
-            _wgrad(rt, dq, x2, d, wq, bq)
-        else:
-            _write_grad(wo, ds2.t() @ o.reshape(M, d), rt)
-            _ready(rt, wo)
-            do = (ds2 @ wo.master).view(B, T, heads, hd)
-            dqh, dk, dv = _ref_attn_bwd(q.view(B, T, heads, hd), kv5[:, :, 0], kv5[:, :, 1], aux,
-                                        do, scale)
-            g5[:, :, 0] = dk
-            g5[:, :, 1] = dv
-            dq = dqh.reshape(M, d)
-            _write_grad(wq, dq.t() @ x2, rt)
-            _write_grad(bq, dq.sum(0), rt)
-            _ready(rt, wq, bq)  # (GPU: reported by _wgrad / the deferred flush)
-        dx = _dgrad_res(dq, wq, d, dh)
+                kvh.buf = torch.empty(B * S, NKV, dtype=kv_all.dtype, device=dy.device)
+            kv, dkv_all = kv_all, kvh.buf.view(B, S, -1)
+        ext = _ExtKV(_layer_kv(kv, layer, d, heads), *ctx.kv8, _layer_kv(dkv_all, layer, d, heads),
+                     _layer_kv(kvh.buf8, layer, d, heads), gk, kvh.part, cs_k, cs_v)
+        dx = _attn_block_bwd(ctx, dy, x2, q, o, aux, kv_len, ext)
         # Only layer 0 hands the (by then complete) shared buffer to autograd;
         # the other layers contribute through the side channel, so no adds.
-        dkv_ret = dkv_all if layer == 0 else None
-        return (dx.view(B, T, d), dkv_ret) + (None,) * CrossAttnBlockFn.NO_GRAD_ARGS
+        dkv_ret = None
+        if layer == 0:  # (kvh.f8b: autograd gets a zero-stride placeholder of the right shape)
+            dkv_ret = dkv_all if dkv_all is not None else torch.zeros(
+                1, dtype=kv_all.dtype, device=dy.device).expand(kv_all.shape)
+        return (dx, dkv_ret) + (None,) * CrossAttnBlockFn.NO_GRAD_ARGS
 
 
 # =============================================================================== feed-forward block
