@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "tdg_attn.h"
+#include "tdg_chrf.h"
 #include "tdg_decode.h"
 #include "tdg_distill.h"
 #include "tdg_overlap.h"
@@ -76,6 +77,11 @@ int tdg_beam_topk_wide(const tdg::BeamWideArgs* w, hipStream_t st);
 // -1: L outside [1, 512], N or P negative, ld < L; -2: a null operand; nothing
 // launched
 int tdg_ngram_matches(const tdg::NgramArgs* a, hipStream_t st);
+
+// ------------------------------------------------------------------ chrf.hip
+// -1: L outside [1, 2048], N or P negative, ld < L; -2: a null operand; nothing
+// launched
+int tdg_char_ngram_matches(const tdg::ChrfArgs* a, hipStream_t st);
 
 // ---------------------------------------------------------------- norm.hip
 // ctr: device RNG step counter (or null); site: dropout site id; y8 / s8 /

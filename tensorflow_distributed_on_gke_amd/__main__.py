@@ -3,13 +3,15 @@
     python -m tensorflow_distributed_on_gke_amd train [--config FILE] [--set key=value ...] [--nproc N]
     python -m tensorflow_distributed_on_gke_amd test  --weights PREFIX [PREFIX ...] [--ensemble-weights W ...]
             [--ema] [--sentence TEXT ...] [--beam N]
-            [--sample N --temperature T --top-k K --top-p P --seed S] [--mbr]
+            [--sample N --temperature T --top-k K --top-p P --seed S] [--mbr [--mbr-utility bleu|chrf]]
             [--input FILE --output FILE [--batch N] [--n-best]]
     python -m tensorflow_distributed_on_gke_amd score --weights PREFIX [PREFIX ...] [--ensemble-weights W ...]
             [--ema] --input FILE --output FILE [--batch N] [--tokens] [--accuracy]
             [--rerank [--length-penalty A] [--mix L]]
-    python -m tensorflow_distributed_on_gke_amd mbr   --input FILE --output FILE [--lc]
+    python -m tensorflow_distributed_on_gke_amd mbr   --input FILE --output FILE [--lc] [--utility bleu|chrf]
     python -m tensorflow_distributed_on_gke_amd bleu  --hyp FILE --ref FILE [--hyp-field K] [--ref-field K] [--lc]
+    python -m tensorflow_distributed_on_gke_amd chrf  --hyp FILE --ref FILE [--hyp-field K] [--ref-field K] [--lc]
+            [--beta B] [--order K]
     python -m tensorflow_distributed_on_gke_amd average --inputs PREFIX PREFIX ... --output PREFIX
     python -m tensorflow_distributed_on_gke_amd heartbeat --port 3479
 
@@ -36,7 +38,9 @@ equal) at every step; --ema then applies to every prefix. With --beam N
 source is kept by minimum-Bayes-risk selection (infer/mbr.py): of the N
 candidates the one with the highest mean smoothed sentence BLEU against all of
 them; the file then holds source<TAB>hypothesis<TAB>model score<TAB>expected
-utility lines.
+utility lines. --mbr-utility chrf takes chrF over the detokenised candidates'
+characters as the utility instead (infer/chrf.py), the usual choice among
+samples; the fourth field is then the expected chrF, in [0, 1].
 `score` is teacher-forced scoring (infer/score.py): how probable the model, or
 the ensemble, finds each target of source<TAB>target[<TAB>...] lines (the
 output of `test --input` is such a file). It writes
@@ -51,7 +55,8 @@ first, with that key as its third field.
 `mbr` is the same selection on text, without a model: of every run of
 source<TAB>candidate[<TAB>...] lines with equal source it writes
 source<TAB>best candidate<TAB>expected utility, ties to the first; the units are
-the candidates' whitespace-separated words (--lc: lowercased first).
+the candidates' whitespace-separated words (--lc: lowercased first), or, with
+--utility chrf, their characters without whitespace under the chrF utility.
 `bleu` is corpus BLEU (infer/bleu.py) of --hyp against --ref, one reference
 per line, over whitespace-separated words AS GIVEN: no tokenisation or
 detokenisation is applied (a "tokenize none" BLEU; tokenise both files
@@ -59,6 +64,11 @@ beforehand to compare with other tools). --hyp-field / --ref-field K take the
 K-th tab-separated column (1-based; default: the whole line), so `--hyp out.tsv
 --hyp-field 2` reads the output of `test --input`. It prints one line: BLEU, the
 four n-gram precisions, brevity penalty, length ratio and both lengths.
+`chrf` is corpus chrF (infer/chrf.py) of the same files, read the same way: the
+F-score of character n-grams up to --order K (default 6) over the lines'
+characters without whitespace, recall weighted --beta B (default 2) times
+precision. It prints one line: chrF, precision, recall, orders and the two
+character counts. No word n-grams (chrF++).
 `average` is checkpoint averaging: the mean of several weight bundles (float64
 on the host) as one f32 bundle `test --weights` and `warm_start` load.
 """
@@ -169,6 +179,8 @@ def cmd_test(args) -> int:
         mode["n_best"] = True
     if args.mbr:
         mode["mbr"] = True
+    if args.mbr_utility != "bleu":
+        mode["mbr_utility"] = args.mbr_utility
     if args.input:
         # file mode: source<TAB>hypothesis<TAB>score, input order, `sample` (or, with
         # --n-best, `beam`) lines per source; --mbr: one, with its expected utility
@@ -285,7 +297,7 @@ def cmd_mbr(args) -> int:
 
     sources, groups = args.groups
     try:
-        picked = select_text(groups, lowercase=args.lc, device=_device(args.device))
+        picked = select_text(groups, lowercase=args.lc, device=_device(args.device), utility=args.utility)
     except ValueError as e:
         print(f"mbr: {args.input}: {e}", file=sys.stderr)
         return 2
@@ -320,6 +332,19 @@ def cmd_bleu(args) -> int:
         print(f"bleu: {e}", file=sys.stderr)
         return 2
     print(format_bleu(b))
+    return 0
+
+
+def cmd_chrf(args) -> int:
+    from tensorflow_distributed_on_gke_amd.infer.chrf import corpus_chrf, format_chrf
+
+    try:
+        c = corpus_chrf(args.hyp_lines, args.ref_lines, lowercase=args.lc, beta=args.beta, order=args.order,
+                        device=_device(args.device))
+    except ValueError as e:
+        print(f"chrf: {e}", file=sys.stderr)
+        return 2
+    print(format_chrf(c))
     return 0
 
 
@@ -382,6 +407,8 @@ def main(argv=None) -> int:
     e.add_argument("--mbr", action="store_true",
                    help="with --sample N or --beam N (N >= 2): keep the candidate of highest expected "
                         "utility; file mode adds that utility as a fourth field")
+    e.add_argument("--mbr-utility", choices=("bleu", "chrf"), default="bleu",
+                   help="the utility of --mbr: sentence BLEU over tokens, or chrF over characters")
     sc = sub.add_parser("score", parents=[common, models])
     sc.add_argument("--input", default=None, metavar="FILE",
                     help="source<TAB>target[<TAB>...] lines (the output of test --input is one)")
@@ -402,6 +429,8 @@ def main(argv=None) -> int:
     mb.add_argument("--output", required=True, metavar="FILE",
                     help="source<TAB>best candidate<TAB>expected utility, one line per source")
     mb.add_argument("--lc", action="store_true", help="lowercase the candidates first")
+    mb.add_argument("--utility", choices=("bleu", "chrf"), default="bleu",
+                    help="sentence BLEU over words, or chrF over characters")
     mb.add_argument("--device", default="auto")
     bl = sub.add_parser("bleu")
     bl.add_argument("--hyp", required=True, metavar="FILE")
@@ -411,6 +440,16 @@ def main(argv=None) -> int:
     bl.add_argument("--ref-field", type=int, default=0, metavar="K")
     bl.add_argument("--lc", action="store_true", help="lowercase both sides first")
     bl.add_argument("--device", default="auto")
+    cf = sub.add_parser("chrf")
+    cf.add_argument("--hyp", required=True, metavar="FILE")
+    cf.add_argument("--ref", required=True, metavar="FILE", help="one reference per hypothesis line")
+    cf.add_argument("--hyp-field", type=int, default=0, metavar="K",
+                    help="the K-th tab-separated column of --hyp (1-based; default: the whole line)")
+    cf.add_argument("--ref-field", type=int, default=0, metavar="K")
+    cf.add_argument("--lc", action="store_true", help="lowercase both sides first")
+    cf.add_argument("--beta", type=float, default=2.0, help="weight of recall against precision")
+    cf.add_argument("--order", type=int, default=6, help="longest character n-gram, 1 to 6")
+    cf.add_argument("--device", default="auto")
     a = sub.add_parser("average")
     a.add_argument("--inputs", nargs="+", required=True, metavar="PREFIX",
                    help="weight bundles (prefixes or snapshot directories) of one model")
@@ -448,7 +487,8 @@ def main(argv=None) -> int:
             ap.error("test: --n-best lists the hypotheses of --beam N > 1 in file mode (--input)")
         from tensorflow_distributed_on_gke_amd.infer.greedy import check_mode
         try:  # the library's own rules, before any model is built
-            check_mode(beam=args.beam, sample=args.sample, n_best=args.n_best, mbr=args.mbr)
+            check_mode(beam=args.beam, sample=args.sample, n_best=args.n_best, mbr=args.mbr,
+                       mbr_utility=args.mbr_utility)
         except ValueError as e:
             ap.error(f"test: {e}")
     if args.cmd == "mbr":
@@ -456,21 +496,23 @@ def main(argv=None) -> int:
             args.groups = _read_candidates(args.input)
         except (OSError, ValueError) as e:
             ap.error(f"mbr: {e}")
-    if args.cmd == "bleu":
+    if args.cmd == "chrf" and not (1 <= args.order <= 6 and args.beta > 0):
+        ap.error("chrf: --order is 1 to 6 and --beta > 0")
+    if args.cmd in ("bleu", "chrf"):
         if args.hyp_field < 0 or args.ref_field < 0:
-            ap.error("bleu: --hyp-field and --ref-field count columns from 1")
+            ap.error(f"{args.cmd}: --hyp-field and --ref-field count columns from 1")
         try:
             args.hyp_lines = _read_field(args.hyp, args.hyp_field)
             args.ref_lines = _read_field(args.ref, args.ref_field)
         except (OSError, ValueError) as e:
-            ap.error(f"bleu: {e}")
+            ap.error(f"{args.cmd}: {e}")
         if len(args.hyp_lines) != len(args.ref_lines):
-            ap.error(f"bleu: {args.hyp} has {len(args.hyp_lines)} lines, {args.ref} "
+            ap.error(f"{args.cmd}: {args.hyp} has {len(args.hyp_lines)} lines, {args.ref} "
                      f"{len(args.ref_lines)}")
     if args.cmd == "test" and not args.sentence and not args.input:
         args.sentence = ["muitas pessoas vieram à estação."]  # reference test.py:9
     return {"train": cmd_train, "test": cmd_test, "score": cmd_score, "mbr": cmd_mbr, "bleu": cmd_bleu,
-            "average": cmd_average, "heartbeat": cmd_heartbeat}[args.cmd](args)
+            "chrf": cmd_chrf,             "average": cmd_average, "heartbeat": cmd_heartbeat}[args.cmd](args)
 
 
 if __name__ == "__main__":

@@ -20,7 +20,9 @@ import torch
 
 from tensorflow_distributed_on_gke_amd.infer.beam import beam_search, length_penalty
 from tensorflow_distributed_on_gke_amd.infer.ensemble import Ensemble, members
-from tensorflow_distributed_on_gke_amd.infer.mbr import mbr_select
+from tensorflow_distributed_on_gke_amd.infer.chrf import char_units, pack_rows
+from tensorflow_distributed_on_gke_amd.infer.mbr import UTILITIES, mbr_chrf, mbr_select
+from tensorflow_distributed_on_gke_amd.ops.kernels.chrf import CHRF_MAX_L
 from tensorflow_distributed_on_gke_amd.infer.sample import sample_search
 from tensorflow_distributed_on_gke_amd.infer.score import score_pairs
 from tensorflow_distributed_on_gke_amd.infer.step import DecoderStep
@@ -29,7 +31,8 @@ from tensorflow_distributed_on_gke_amd.models.layers import CrossKVFn, EmbedFn, 
 from tensorflow_distributed_on_gke_amd.models.transformer import PAD_ID, Transformer, seq_lengths
 
 
-def check_mode(beam: int = 1, sample: int = 0, n_best: bool = False, mbr: bool = False, **_) -> None:
+def check_mode(beam: int = 1, sample: int = 0, n_best: bool = False, mbr: bool = False,
+               mbr_utility: str = "bleu", **_) -> None:
     """The rules between the decoding modes of `Tester.decode`, or ValueError;
     its other arguments are accepted and do not matter here."""
     if sample < 0:
@@ -42,6 +45,10 @@ def check_mode(beam: int = 1, sample: int = 0, n_best: bool = False, mbr: bool =
         raise ValueError("mbr keeps one hypothesis per sentence: it does not go with n_best")
     if mbr and max(sample, beam) < 2:
         raise ValueError("mbr selects among candidates: it needs sample >= 2 or beam >= 2")
+    if mbr_utility not in UTILITIES:
+        raise ValueError(f"mbr_utility must be one of {UTILITIES}, got {mbr_utility!r}")
+    if mbr_utility != "bleu" and not mbr:
+        raise ValueError("mbr_utility belongs to mbr")
 
 
 def _append_argmax(out: torch.Tensor, done: torch.Tensor, lg: torch.Tensor, end: int):
@@ -137,7 +144,8 @@ class Tester:
     def decode(self, src: torch.Tensor, max_length: int = 20, kv_cache: bool = True, beam: int = 1,
                alpha: float = 0.6, sample: int = 0, temperature: float = 1.0, top_k: int = 0,
                top_p: float = 1.0, seed: int = 0, row_id0: int = 0, n_best: bool = False,
-               mbr: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+               mbr: bool = False, mbr_utility: str = "bleu"
+               ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """src int64 [B, S] -> (tokens int64 [B, n, 1 + len] on the CPU, scores
         f32 [B, n] or None): greedy (n = 1, no scores), beam search (beam > 1:
         n = 1, the best hypothesis; with `n_best` n = beam, all of them by
@@ -147,14 +155,16 @@ class Tester:
         is an error), and its greedy mode is beam search of width 1 with
         alpha 0, whose score is returned. `mbr`: of the `sample` draws, or of
         the beam's hypotheses, the one of highest expected utility
-        (`decode_mbr`), in the n = 1 form, with its model score."""
-        check_mode(beam=beam, sample=sample, n_best=n_best, mbr=mbr)
+        (`decode_mbr`, with `mbr_utility` as its utility), in the n = 1 form,
+        with its model score."""
+        check_mode(beam=beam, sample=sample, n_best=n_best, mbr=mbr, mbr_utility=mbr_utility)
         ensemble = isinstance(self.model, Ensemble)
         if ensemble and not kv_cache:
             raise ValueError("an ensemble decodes with the K/V cache: kv_cache=False is not supported")
         draw = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, row_id0=row_id0)
         if mbr:
-            return self.decode_mbr(src, max_length, beam=beam, alpha=alpha, sample=sample, **draw)[:2]
+            return self.decode_mbr(src, max_length, beam=beam, alpha=alpha, sample=sample,
+                                   utility=mbr_utility, **draw)[:2]
         if sample > 0 or beam > 1 or ensemble:
             tokens, scores, best = self._candidates(src, max_length, beam, alpha if beam > 1 else 0.0,
                                                     sample, **draw)
@@ -187,21 +197,33 @@ class Tester:
 
     def decode_mbr(self, src: torch.Tensor, max_length: int = 20, beam: int = 1, alpha: float = 0.6,
                    sample: int = 0, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
-                   seed: int = 0, row_id0: int = 0
+                   seed: int = 0, row_id0: int = 0, utility: str = "bleu"
                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Minimum-Bayes-risk decoding (infer/mbr.py): the candidates of a
         sentence are its `sample` >= 2 draws, or the hypotheses of its beam
         search of width `beam` >= 2 (slots of score -inf, which never held
         one, left out), and the one closest to all of them is kept. Selection
         runs on the device tokens, before anything is copied to the host.
+        `utility` "chrf": the utility is chrF over characters instead of
+        sentence BLEU over tokens; the candidates' token rows are copied out
+        and detokenised with the target tokenizer, whichever it is, and the
+        strings' code points without whitespace go back to the device.
         src int64 [B, S] -> (tokens int64 [B, 1, 1 + len], the kept
         candidate's model score f32 [B, 1], its expected utility f64 [B]), on
         the CPU."""
-        check_mode(beam=beam, sample=sample, mbr=True)
+        check_mode(beam=beam, sample=sample, mbr=True, mbr_utility=utility)
         tokens, scores, _ = self._candidates(src, max_length, beam, alpha, sample, temperature=temperature,
                                              top_k=top_k, top_p=top_p, seed=seed, row_id0=row_id0)
         valid = None if sample > 0 else scores > float("-inf")
-        best, expected = mbr_select(tokens, self.tgt_tok.start_end()[1], PAD_ID, valid)
+        if utility == "chrf":
+            B, n = tokens.shape[:2]
+            rows = [char_units(self._text(row)[0]) for cands in tokens.cpu().tolist() for row in cands]
+            if max(len(r) for r in rows) > CHRF_MAX_L:
+                raise ValueError(f"decode_mbr: a candidate of more than {CHRF_MAX_L} characters")
+            chr_, length = pack_rows(rows)
+            best, expected = mbr_chrf(chr_.to(tokens.device), length.to(tokens.device), B, n, valid)
+        else:
+            best, expected = mbr_select(tokens, self.tgt_tok.start_end()[1], PAD_ID, valid)
         pick = best.view(-1, 1)
         kept = tokens.gather(1, pick.unsqueeze(-1).expand(-1, 1, tokens.shape[2]))
         return kept.cpu(), scores.gather(1, pick).cpu(), expected.gather(1, pick).view(-1).cpu()
@@ -245,7 +267,8 @@ class Tester:
             src = self.src_tok.tokenize([lines[i] for i in idx])
             kw = dict(mode, row_id0=[i * n for i in idx]) if mode.get("sample", 0) > 0 else mode
             if mbr:
-                kw = {k: v for k, v in kw.items() if k not in ("mbr", "kv_cache")}
+                kw = {k: v for k, v in kw.items() if k not in ("mbr", "kv_cache", "mbr_utility")}
+                kw["utility"] = mode.get("mbr_utility", "bleu")
                 tokens, scores, utility = self.decode_mbr(src, max_length, **kw)
                 for j, i in enumerate(idx):
                     out[i] = [(self._text(tokens[j, 0].tolist())[0], float(scores[j, 0]),
@@ -307,19 +330,20 @@ class Tester:
 
     def __call__(self, sentence: Union[str, Sequence[str]], max_length: int = 20, kv_cache: bool = True,
                  beam: int = 1, alpha: float = 0.6, sample: int = 0, temperature: float = 1.0,
-                 top_k: int = 0, top_p: float = 1.0, seed: int = 0, mbr: bool = False
-                 ) -> Tuple[Union[str, List[str]], list, Dict[str, torch.Tensor]]:
+                 top_k: int = 0, top_p: float = 1.0, seed: int = 0, mbr: bool = False,
+                 mbr_utility: str = "bleu") -> Tuple[Union[str, List[str]], list, Dict[str, torch.Tensor]]:
         """beam > 1: beam search (infer/beam.py) with length penalty `alpha`
         instead of the greedy argmax; the return value has the same form.
         sample > 0: `sample` translations per sentence drawn with temperature,
         top-k and top-p (infer/sample.py); texts and tokens are then a list per
         sentence, the attention maps those of every sentence's first sample.
         mbr: of those samples, or of the beam's hypotheses, the one `decode_mbr`
-        keeps, in the form of the greedy result."""
+        keeps (`mbr_utility`: "bleu" or "chrf"), in the form of the greedy result."""
         single = isinstance(sentence, str)
         src = self.src_tok.tokenize(sentence)
         out, _ = self.decode(src, max_length, kv_cache=kv_cache, beam=beam, alpha=alpha, sample=sample,
-                             temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, mbr=mbr)
+                             temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, mbr=mbr,
+                             mbr_utility=mbr_utility)
         many = sample > 0 and not mbr
         texts, tokens = [], []
         for rows in out.tolist():

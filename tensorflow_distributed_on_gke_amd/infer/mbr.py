@@ -9,6 +9,11 @@ returns the clipped n-gram match counts; u(i, j) and u(j, i) come from the same
 counts, the diagonal from the lengths. What follows the counts is a handful of
 f64 torch ops on the tokens' device: no per-group host loop, no device-to-host
 copy.
+
+The second utility is chrF (infer/chrf.py) over the candidates' characters,
+the usual choice among 16 to 64 samples, where sentence BLEU is mostly zeros
+and ties from 3-grams up: the same scheme on `ops.kernels.chrf.
+char_ngram_matches` (csrc/kernels/chrf.hip) and `sentence_chrf`.
 """
 from __future__ import annotations
 
@@ -16,8 +21,12 @@ from typing import Optional, Tuple
 
 import torch
 
+from tensorflow_distributed_on_gke_amd.infer.chrf import char_units, pack_rows, sentence_chrf
 from tensorflow_distributed_on_gke_amd.infer.tokenizer import after_first_end
+from tensorflow_distributed_on_gke_amd.ops.kernels.chrf import CHRF_MAX_L, CHRF_ORDERS, char_ngram_matches
 from tensorflow_distributed_on_gke_amd.ops.kernels.overlap import NGRAM_MAX_L, ngram_matches
+
+UTILITIES = ("bleu", "chrf")
 
 
 def sentence_bleu(m: torch.Tensor, len_h: torch.Tensor, len_r: torch.Tensor) -> torch.Tensor:
@@ -57,24 +66,27 @@ def candidate_rows(tokens: torch.Tensor, end: int, pad_id: int) -> Tuple[torch.T
     return body.reshape(B * n, T).to(torch.int32), length.reshape(B * n).to(torch.int32)
 
 
-def pairwise_utility(tok: torch.Tensor, length: torch.Tensor, B: int, n: int) -> torch.Tensor:
+def pairwise_utility(tok: torch.Tensor, length: torch.Tensor, B: int, n: int,
+                     utility: str = "bleu") -> torch.Tensor:
     """f64 [B, n, n]: u[b, i, j] = sentence_bleu of candidate i of group b as
     the hypothesis against candidate j as the reference (rows b * n + i of
-    tok / length)."""
+    tok / length); `utility` "chrf": sentence_chrf, the rows being code points."""
     dev = tok.device
     iu = torch.triu_indices(n, n, 1, device=dev)
     base = (torch.arange(B, device=dev) * n).view(B, 1)
     pair_a = (base + iu[0]).reshape(-1).to(torch.int32)
     pair_b = (base + iu[1]).reshape(-1).to(torch.int32)
-    m = ngram_matches(tok, length, pair_a, pair_b).view(B, -1, 4)
+    count, K, score = ((ngram_matches, 4, sentence_bleu) if utility == "bleu" else
+                       (char_ngram_matches, CHRF_ORDERS, sentence_chrf))
+    m = count(tok, length, pair_a, pair_b).view(B, -1, K)
     ln = length.view(B, n).long()
-    M = torch.empty(B, n, n, 4, dtype=torch.int32, device=dev)
+    M = torch.empty(B, n, n, K, dtype=torch.int32, device=dev)
     M[:, iu[0], iu[1]] = m
     M[:, iu[1], iu[0]] = m
     d = torch.arange(n, device=dev)
     # a row against itself: every n-gram it has
-    M[:, d, d] = (ln.unsqueeze(-1) - torch.arange(4, device=dev)).clamp(min=0).to(torch.int32)
-    return sentence_bleu(M, ln.view(B, n, 1), ln.view(B, 1, n))
+    M[:, d, d] = (ln.unsqueeze(-1) - torch.arange(K, device=dev)).clamp(min=0).to(torch.int32)
+    return score(M, ln.view(B, n, 1), ln.view(B, 1, n))
 
 
 @torch.no_grad()
@@ -94,7 +106,24 @@ def mbr_select(tokens: torch.Tensor, end: int, pad_id: int, valid: Optional[torc
     dev = tokens.device
     valid = torch.ones(B, n, dtype=torch.bool, device=dev) if valid is None else valid.to(dev)
     tok, length = candidate_rows(tokens, end, pad_id)
-    u = pairwise_utility(tok, length, B, n)
+    return _select(pairwise_utility(tok, length, B, n), valid)
+
+
+@torch.no_grad()
+def mbr_chrf(chr_: torch.Tensor, length: torch.Tensor, B: int, n: int,
+             valid: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`mbr_select` with the chrF utility, on rows of code points: chr_ int32
+    [B * n, L] (L <= 2048), length int32 [B * n], row b * n + i = candidate i
+    of group b -> (best, expected) as `mbr_select` returns them."""
+    dev = chr_.device
+    valid = torch.ones(B, n, dtype=torch.bool, device=dev) if valid is None else valid.to(dev)
+    return _select(pairwise_utility(chr_, length, B, n, utility="chrf"), valid)
+
+
+def _select(u: torch.Tensor, valid: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Pairwise utilities f64 [B, n, n] and the valid mask -> (best, expected) of `mbr_select`."""
+    B, n = valid.shape
+    dev = u.device
     count = valid.sum(dim=1).clamp(min=1).double().view(B, 1)
     expected = (u * valid.double().view(B, 1, n)).sum(dim=2) / count
     expected = expected.masked_fill(~valid, float("-inf"))
@@ -104,14 +133,50 @@ def mbr_select(tokens: torch.Tensor, end: int, pad_id: int, valid: Optional[torc
     return best, expected
 
 
-def select_text(groups, lowercase: bool = False, device=None, pairs_per_launch: int = 1 << 22):
+def _select_chrf(groups, lowercase: bool, dev: torch.device):
+    """`select_text` with the chrF utility: a candidate's row is its code
+    points without whitespace, all groups go through one `mbr_chrf`."""
+    rows = []
+    for g, cands in enumerate(groups):
+        if not cands:
+            raise ValueError(f"group {g + 1} has no candidate")
+        for k, c in enumerate(cands):
+            u = char_units(c, lowercase)
+            if len(u) > CHRF_MAX_L:
+                raise ValueError(f"candidate {k + 1} of group {g + 1} has {len(u)} characters, more "
+                                 f"than {CHRF_MAX_L}")
+            rows.append(u)
+    if not groups:
+        return []
+    sizes = torch.tensor([len(g) for g in groups])
+    B, n = len(groups), int(sizes.max())
+    valid = torch.arange(n).view(1, n) < sizes.view(B, 1)
+    packed, length = pack_rows(rows)
+    chr_ = torch.zeros(B, n, packed.shape[1], dtype=torch.int32)
+    ln = torch.zeros(B, n, dtype=torch.int32)
+    chr_[valid], ln[valid] = packed, length
+    best, expected = mbr_chrf(chr_.view(B * n, -1).to(dev), ln.view(-1).to(dev), B, n, valid.to(dev))
+    util = expected.gather(1, best.view(B, 1)).view(B)
+    return list(zip(best.tolist(), util.tolist()))
+
+
+def select_text(groups, lowercase: bool = False, device=None, pairs_per_launch: int = 1 << 22,
+                utility: str = "bleu"):
     """MBR selection among candidate strings, without a model: `groups` is a
     list of candidate lists, a candidate's units are its whitespace-separated
     words (`lowercase` folds case first) -> per group (index of the kept
     candidate, its expected utility), ties to the first. Groups of unequal
     size are padded with invalid slots; about `pairs_per_launch` candidate
     pairs go through one `mbr_select`. A candidate of more than 512 words is
-    a ValueError that names its group and position."""
+    a ValueError that names its group and position. `utility` "chrf": the
+    units are the candidate's code points without whitespace (at most 2048),
+    u(i, j) is `infer.chrf.sentence_chrf` of i against j, and all groups go
+    through one launch; everything else is the same."""
+    if utility not in UTILITIES:
+        raise ValueError(f"utility must be one of {UTILITIES}, got {utility!r}")
+    dev = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
+    if utility == "chrf":
+        return _select_chrf(groups, lowercase, dev)
     PAD, END, FIRST = 0, 1, 2
     ids: dict = {}
     rows = []
@@ -124,7 +189,6 @@ def select_text(groups, lowercase: bool = False, device=None, pairs_per_launch: 
                 raise ValueError(f"candidate {k + 1} of group {g + 1} has {len(words)} words, more "
                                  f"than {NGRAM_MAX_L}")
             rows.append([ids.setdefault(w, len(ids) + FIRST) for w in words])
-    dev = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
     out = []
     g0 = r0 = 0
     while g0 < len(groups):
