@@ -14,6 +14,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   def_fp8(m);
   def_loss(m);
   def_distill(m);
+  def_rdrop(m);
   def_optimizer(m);
   def_ema(m);
   def_signal(m);

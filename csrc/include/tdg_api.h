@@ -14,6 +14,7 @@
 #include "tdg_decode.h"
 #include "tdg_distill.h"
 #include "tdg_overlap.h"
+#include "tdg_rdrop.h"
 
 extern "C" {
 
@@ -140,6 +141,11 @@ int tdg_xent_stats(const float* row_loss, const float* row_correct, int M, const
 // -1: T outside [1, 8], V outside [1, 65536] or alpha outside [0, 1]; -2: a
 // student or teacher row shorter than V, a null teacher; nothing launched
 int tdg_xent_distill(const tdg::DistillArgs* a, hipStream_t st);
+
+// ---------------------------------------------------------------- rdrop.hip
+// -1: V outside [1, 65536], alpha negative or not finite, M < 0; -2: a row
+// shorter than V, a null operand; nothing launched. M == 0 launches nothing
+int tdg_xent_rdrop(const tdg::RdropArgs* a, hipStream_t st);
 
 // ---------------------------------------------------------------- adam.hip
 // gstate: device state of the gradient-norm pass (clip factor, skip flag) or null

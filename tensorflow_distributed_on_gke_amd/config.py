@@ -149,6 +149,15 @@ class Settings:
     distill_weights: Optional[str] = None
     distill_alpha: Optional[float] = None
     distill_preset: Optional[str] = None
+    # extension, off at 0: R-Drop consistency training (Liang et al. 2021;
+    # Transformer.loss_and_backward). rdrop_alpha > 0: every batch goes through
+    # the model twice under two dropout masks and the symmetric KL between the
+    # two next-token distributions, times rdrop_alpha / 2, is added to both
+    # label cross entropies (the paper's NMT value is 5). The step processes
+    # twice the rows: halve local_batch_size / batch_tokens to keep its size.
+    # Finite and >= 0; not with dtype=fp8 or a distillation teacher.
+    # Validation stays the plain one
+    rdrop_alpha: float = 0.0
 
     def global_batch(self, world: int) -> int:
         return self.local_batch_size * world
@@ -196,6 +205,7 @@ def load_settings(path: Optional[str] = None, overrides: Optional[List[str]] = N
     check_accum_steps(s.accum_steps, s.dtype)
     check_batch_tokens(s.batch_tokens, s.data, s.length_bucket)
     check_distill(s.distill_teacher, s.distill_weights, s.distill_alpha, s.dtype)
+    check_rdrop(s.rdrop_alpha, s.dtype, bool(s.distill_teacher))
     return s
 
 
@@ -269,3 +279,18 @@ def check_distill(teacher: Any, weights: Any = None, alpha: Any = None, dtype: s
     if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 < float(alpha) <= 1.0:
         raise ValueError(f"distill_alpha must lie in (0, 1], got {alpha!r}")
     return prefixes, w, float(alpha)
+
+
+def check_rdrop(alpha: Any, dtype: str = "bf16", teacher: bool = False) -> float:
+    """rdrop_alpha is a finite number >= 0 (0: off); > 0 is refused with
+    dtype=fp8 and together with a distillation teacher. ValueError otherwise."""
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or \
+            not 0.0 <= float(alpha) < float("inf"):
+        raise ValueError(f"rdrop_alpha must be a finite number >= 0 (0: off), got {alpha!r}")
+    if alpha > 0 and dtype == "fp8":
+        raise ValueError(f"rdrop_alpha={alpha} with dtype=fp8 is not supported: the R-Drop step "
+                         "trains in bf16 (use dtype=bf16)")
+    if alpha > 0 and teacher:
+        raise ValueError(f"rdrop_alpha={alpha} together with distill_teacher is not supported: "
+                         "one objective beside the label cross entropy at a time")
+    return float(alpha)

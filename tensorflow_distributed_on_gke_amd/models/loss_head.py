@@ -1,11 +1,11 @@
 """The loss head of Transformer.loss_and_backward: vocabulary projection,
-masked cross entropy / accuracy (or the distillation mixture), the final
-layer's gradients and the gradient of the decoder output.
+masked cross entropy / accuracy (or the distillation mixture, or the R-Drop
+paired-row loss), the final layer's gradients and the gradient of the decoder output.
 
 Two functions, one per device: gpu_head sequences the HIP kernels, cpu_head is
 the f32 PyTorch definition the CPU tests hold them to. Each writes `step_out`
 ([loss / workers, accuracy]), adds its record to `accum` ([sum loss, sum acc,
-n, n labels]) and, under distillation, the label cross entropy's to
+n, n labels]) and, under distillation and R-Drop, the label cross entropy's to
 `label_accum`; writes the final layer's gradients (adds to them with
 rt.accumulate); and returns the gradient of `dec` as [B*T, d_model], or None
 without `backward`.
@@ -13,6 +13,10 @@ without `backward`.
 The loss divisor is resolved once per head: the batch's own label count,
 unless `ntok_total` (the count of a whole accumulated update) replaces it or
 the `ntok_sum` all-reduce turns it into the count over all replicas.
+
+R-Drop (rdrop_alpha > 0): `dec` and `labels` are those of the doubled batch,
+copy 2 after copy 1, so logits row i and row i + M (M = half the rows) are one
+pair, and every count is that of both copies.
 """
 from __future__ import annotations
 
@@ -20,15 +24,17 @@ import torch
 
 from tensorflow_distributed_on_gke_amd.models.layers import _dgrad_res, _wgrad
 from tensorflow_distributed_on_gke_amd.ops import kernels as K
+from tensorflow_distributed_on_gke_amd.ops.kernels.loss import rdrop_rows, xent_rdrop
 
 PAD_ID = 0
 
 
 def gpu_head(model, rt, dec, labels, ntok, ntok_work, ntok_total, workers, step_out, accum,
-             label_accum, backward, t_logits, teacher, alpha):
+             label_accum, backward, t_logits, teacher, alpha, rdrop_alpha=0.0):
     """ntok: this batch's label count from prep_batch; ntok_work: the handle
     of its all-reduce, started before the forward (or None); t_logits: the
-    teacher's logits (None: no distillation)."""
+    teacher's logits (None: no distillation); rdrop_alpha > 0: the batch is a
+    doubled one."""
     cfg = model.cfg
     dev = dec.device
     M = labels.numel()
@@ -49,6 +55,12 @@ def gpu_head(model, rt, dec, labels, ntok, ntok_work, ntok_total, workers, step_
                        row_lab, write_grad=backward)
         if label_accum is not None:
             K.xent_stats(row_lab, row_cor, ntok, workers, None, label_accum)
+    elif rdrop_alpha > 0.0:
+        row_lab = K.workspace("row_label", M, dev)[:M]
+        xent_rdrop(logits, cfg.tgt_vocab, labels, ntok, workers, cfg.label_smoothing, rdrop_alpha,
+                   row_loss, row_cor, row_lab, write_grad=backward)
+        if label_accum is not None:
+            K.xent_stats(row_lab, row_cor, ntok, workers, None, label_accum)
     else:
         K.xent(logits, cfg.tgt_vocab, labels, ntok, workers, cfg.label_smoothing, row_loss,
                row_cor, write_grad=backward)
@@ -61,10 +73,11 @@ def gpu_head(model, rt, dec, labels, ntok, ntok_work, ntok_total, workers, step_
 
 
 def cpu_head(model, rt, dec, labels, ntok_sum, ntok_total, workers, step_out, accum,
-             label_accum, backward, t_logits, teacher, alpha):
+             label_accum, backward, t_logits, teacher, alpha, rdrop_alpha=0.0):
     """ntok_sum: called with this replica's label count, turns it in place
     into the count over all replicas (or None); t_logits: the teacher's
-    logits (None: no distillation)."""
+    logits (None: no distillation); rdrop_alpha > 0: the batch is a doubled
+    one."""
     cfg = model.cfg
     dec2 = dec.detach().reshape(labels.numel(), cfg.d_model)
     lg = model.project(dec.detach())
@@ -90,6 +103,11 @@ def cpu_head(model, rt, dec, labels, ntok_sum, ntok_total, workers, step_out, ac
             label_accum += torch.stack([label_loss, acc, torch.tensor(1.0), ntok])
         target = K.distill_target(t_logits, cfg.tgt_vocab, lab, eps, alpha, teacher.weights)
         row_loss = -(target * logp).sum(dim=-1) * mask
+    elif rdrop_alpha > 0.0:
+        if label_accum is not None:
+            label_loss = row_loss.sum() / ntok / workers
+            label_accum += torch.stack([label_loss, acc, torch.tensor(1.0), ntok])
+        row_loss, _, _, dl_rdrop = rdrop_rows(lg, cfg.tgt_vocab, lab, ntok, workers, eps, rdrop_alpha)
     loss = row_loss.sum() / ntok / workers
     step_out.copy_(torch.stack([loss, acc]).detach())
     if accum is not None:
@@ -98,10 +116,12 @@ def cpu_head(model, rt, dec, labels, ntok_sum, ntok_total, workers, step_out, ac
         return None
     if t_logits is not None:
         dl = torch.softmax(lg, -1) - target
+    elif rdrop_alpha > 0.0:
+        dl = None  # (rdrop_rows has masked and divided it)
     else:
         onehot = torch.nn.functional.one_hot(lab, cfg.tgt_vocab).to(torch.float32)
         dl = (torch.softmax(lg, -1) - (1 - eps) * onehot - eps / cfg.tgt_vocab)
-    dl = dl * (mask / (ntok * workers)).view(-1, 1)
+    dl = dl_rdrop if dl is None else dl * (mask / (ntok * workers)).view(-1, 1)
     fw, fb = model.final.w, model.final.b
     g_w = dl.t() @ dec2
     g_b = dl.sum(0)

@@ -300,7 +300,8 @@ class Transformer:
                           bump_ctr: bool = False, ntok_sum=None,
                           ntok_total: Optional[torch.Tensor] = None, teacher=None,
                           alpha: float = 0.0,
-                          label_accum: Optional[torch.Tensor] = None) -> torch.Tensor:
+                          label_accum: Optional[torch.Tensor] = None,
+                          rdrop_alpha: float = 0.0) -> torch.Tensor:
         """Teacher-forced forward, masked CE / accuracy, and (if `backward`)
         the full backward into the flat gradient buffer. Returns a device
         tensor [local_loss, accuracy] (loss already / workers, as the
@@ -322,7 +323,19 @@ class Transformer:
         accum) collects the label cross entropy alone. The teacher's forward
         runs before the student's: the named workspaces are scratch of one
         stream, and nothing may run between the student's forward and
-        backward. Without a teacher or with alpha = 0 this is the plain step."""
+        backward. Without a teacher or with alpha = 0 this is the plain step.
+        rdrop_alpha: R-Drop (Liang et al. 2021). With rdrop_alpha > 0 and
+        `backward`, src and tgt are repeated to 2B rows on the device, copy 2
+        after copy 1, before anything else: lengths, the label count and the
+        dropout counter are those of the doubled batch, the forward is the
+        ordinary one on 2B rows (each copy under its own dropout mask: the
+        keep decision is keyed by the element's position in the 2B-row
+        tensor), and the loss is ops.kernels.loss.xent_rdrop on the pairs
+        (row i, row i + B*T): both label cross entropies plus rdrop_alpha / 2
+        times the symmetric KL between the copies' next-token distributions.
+        The returned loss and `accum` hold that objective per label of the
+        doubled batch, label_accum the label cross entropy alone. Not with
+        fp8 or a teacher. Without `backward` the batch is never doubled."""
         if ntok_total is not None and ntok_sum is not None:
             raise ValueError("loss_and_backward: ntok_total and ntok_sum exclude each other")
         if not 0.0 <= alpha <= 1.0:
@@ -330,6 +343,15 @@ class Transformer:
         distill = teacher is not None and alpha > 0.0
         if distill and rt.fp8 is not None:
             raise ValueError("loss_and_backward: distillation is not supported with dtype=fp8")
+        if not (rdrop_alpha >= 0.0 and math.isfinite(rdrop_alpha)):
+            raise ValueError(f"loss_and_backward: rdrop_alpha must be finite and >= 0, got {rdrop_alpha!r}")
+        rdrop = float(rdrop_alpha) if backward else 0.0
+        if rdrop > 0.0:
+            if rt.fp8 is not None:
+                raise ValueError("loss_and_backward: R-Drop is not supported with dtype=fp8")
+            if distill:
+                raise ValueError("loss_and_backward: R-Drop and distillation exclude each other")
+            src, tgt = torch.cat([src, src]), torch.cat([tgt, tgt])
         dev = src.device
         gpu = dev.type == "cuda"
         ntok = ntok_work = None
@@ -354,10 +376,10 @@ class Transformer:
             dec = self.features(src, tgt_in, rt, lengths)
         if gpu:
             ddec = gpu_head(self, rt, dec, labels, ntok, ntok_work, ntok_total, workers, step_out,
-                            accum, label_accum, backward, t_logits, teacher, alpha)
+                            accum, label_accum, backward, t_logits, teacher, alpha, rdrop)
         else:
             ddec = cpu_head(self, rt, dec, labels, ntok_sum, ntok_total, workers, step_out,
-                            accum, label_accum, backward, t_logits, teacher, alpha)
+                            accum, label_accum, backward, t_logits, teacher, alpha, rdrop)
         if ddec is None:
             return step_out
         dec.backward(ddec.view(B, T, self.cfg.d_model).to(dec.dtype))

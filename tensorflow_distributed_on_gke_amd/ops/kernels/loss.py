@@ -1,5 +1,6 @@
-"""Loss family (csrc/kernels/xent.hip, distill.hip): cross entropy, its
-step statistics, and the word-level distillation loss with its CPU arm."""
+"""Loss family (csrc/kernels/xent.hip, distill.hip, rdrop.hip): cross entropy,
+its step statistics, the word-level distillation loss and the R-Drop paired-row
+loss, the latter two with their CPU arms."""
 from __future__ import annotations
 
 import math
@@ -78,3 +79,64 @@ def xent_distill(logits, teachers, V, labels, ntok, workers, smoothing, alpha, w
         d = (torch.exp(logp) - target) * (valid / (n * workers)).view(-1, 1)
         logits.zero_()
         logits[:, :V] = d.to(logits.dtype)
+
+
+def rdrop_rows(logits2, V: int, labels, ntok, workers: float, smoothing: float, alpha: float):
+    """The R-Drop loss as plain f32 PyTorch (the definition at the head of
+    csrc/kernels/rdrop.hip). logits2 [2 M, >= V], copy 2 after copy 1, rows i
+    and i + M one pair; labels [2 M] (0 = PAD), those of the first copy are
+    read. With p = softmax(xa), r = softmax(xb), d = log p - log r:
+        row_label = (1 - s)(lse - x[y]) + s (lse - mean x)
+        row_loss[a] = row_label[a] + (alpha / 2) sum p d,  row_loss[b] = row_label[b] - (alpha / 2) sum r d
+        dlogits[a] = (p - target + (alpha / 2)(p (d - KLab) + p - r)) / (max(ntok, 1) workers), b likewise
+    Returns (row_loss [2 M], row_label [2 M], row_correct [2 M], dlogits f32
+    [2 M, V]); PAD pairs give zeros throughout."""
+    x = logits2[:, :V].float()
+    M = x.shape[0] // 2
+    lab = labels.reshape(-1)[:M].to(torch.int64)
+    valid = (lab != 0).to(torch.float32)
+    xa, xb = x[:M], x[M:]
+    lsa, lsb = torch.logsumexp(xa, -1, keepdim=True), torch.logsumexp(xb, -1, keepdim=True)
+    la, lb = xa - lsa, xb - lsb
+    p, r = torch.exp(la), torch.exp(lb)
+    d = la - lb
+    klab, klba = (p * d).sum(-1), -(r * d).sum(-1)
+    hard = torch.nn.functional.one_hot(lab, V).to(torch.float32) * (1.0 - smoothing) + smoothing / V
+    lab_a, lab_b = -(hard * la).sum(-1), -(hard * lb).sum(-1)
+    h = 0.5 * alpha
+    row_label = torch.cat([lab_a * valid, lab_b * valid])
+    row_loss = torch.cat([(lab_a + h * klab) * valid, (lab_b + h * klba) * valid])
+    correct = torch.cat([(xa.argmax(-1) == lab).float() * valid, (xb.argmax(-1) == lab).float() * valid])
+    n = torch.as_tensor(ntok, dtype=torch.float32).reshape(-1)[0].clamp_min(1.0)
+    sc = (valid / (n * workers)).view(-1, 1)
+    da = (p - hard + h * (p * (d - klab.view(-1, 1)) + p - r)) * sc
+    db = (r - hard + h * (r * (-d - klba.view(-1, 1)) + r - p)) * sc
+    return row_loss, row_label, correct, torch.cat([da, db])
+
+
+def xent_rdrop(logits2, V, labels, ntok, workers, smoothing, alpha, row_loss, row_correct,
+               row_label=None, write_grad=True):
+    """R-Drop (Liang et al. 2021) loss of a doubled batch, forward and backward
+    in one launch (csrc/kernels/rdrop.hip): logits2 [2 M, ldl], copy 2 after
+    copy 1; per pair (rows i, i + M) the label cross entropy of each row plus
+    (alpha / 2) KL(own || other). Writes row_loss, row_correct, row_label when
+    given (what `xent` writes as row_loss) and, with write_grad, both rows'
+    gradients in place, divided by max(ntok, 1) workers, columns [V, ldl)
+    zeroed. `ntok` counts the labels of both copies. PAD pairs give zeros
+    throughout. GPU: bf16 logits, V <= 65536. CPU: `rdrop_rows`."""
+    if not 1 <= V <= 65536:
+        raise RuntimeError(f"xent_rdrop: V {V} outside [1, 65536]")
+    if not (alpha >= 0.0 and math.isfinite(alpha)):
+        raise RuntimeError(f"xent_rdrop: alpha {alpha} must be finite and >= 0")
+    if logits2.is_cuda:
+        C().xent_rdrop(logits2, V, labels, ntok, workers, smoothing, alpha, row_loss, row_correct,
+                       row_label, write_grad)
+        return
+    rl, rb, rc, d = rdrop_rows(logits2, V, labels, ntok, workers, smoothing, alpha)
+    row_loss.copy_(rl)
+    row_correct.copy_(rc)
+    if row_label is not None:
+        row_label.copy_(rb)
+    if write_grad:
+        logits2.zero_()
+        logits2[:, :V] = d.to(logits2.dtype)

@@ -31,7 +31,11 @@ corpus (data/corpus.py) unless `corpus_on_device` is off, and `fill` and
 `distill_teacher` word-level distillation from frozen teachers
 (train/distill.py), loaded on every rank after the student: the loss fields
 then hold the mixed objective, `label_loss` in the log lines and records the
-label cross entropy alone, and validation stays the plain one.
+label cross entropy alone, and validation stays the plain one; with
+`rdrop_alpha` > 0 R-Drop consistency training (every batch doubled on the
+device, Transformer.loss_and_backward): the loss fields hold the objective,
+`label_loss` the label cross entropy of both copies, tokens/s counts each pair
+once, and validation stays the plain one.
 
 Metric reads are the only host syncs: the device accumulators are summed over
 ranks (one small all-reduce) at log points, not every step.
@@ -50,7 +54,7 @@ import torch.distributed as dist
 from tensorflow_distributed_on_gke_amd.checkpoint import bundle
 from tensorflow_distributed_on_gke_amd.checkpoint.uploader import ModelUploader, make_storage
 from tensorflow_distributed_on_gke_amd.config import (Settings, check_accum_steps, check_batch_tokens,
-                                                      check_distill)
+                                                      check_distill, check_rdrop)
 from tensorflow_distributed_on_gke_amd.data.synthetic import SyntheticPairs
 from tensorflow_distributed_on_gke_amd.models.layers import RunCtx
 from tensorflow_distributed_on_gke_amd.models.transformer import Transformer, model_config
@@ -101,6 +105,7 @@ class Trainer:
         check_batch_tokens(s.batch_tokens, s.data, s.length_bucket)
         t_prefixes, t_weights, t_alpha = check_distill(s.distill_teacher, s.distill_weights,
                                                        s.distill_alpha, s.dtype)
+        rdrop_alpha = check_rdrop(s.rdrop_alpha, s.dtype, bool(t_prefixes))
         if s.worker_count != info.world and info.chief:
             # the reference used worker_count both as expected size and loss
             # divisor; the runtime world size wins
@@ -143,7 +148,9 @@ class Trainer:
                          f"{[round(w, 4) for w in self.teacher.weights]}, alpha {t_alpha}")
         self.step_fn = TrainStep(self.model, self.opt, self.ddp, workers=info.world, seed=s.seed + 17,
                                  fp8_state=self.fp8, loss_mode=s.loss_mode, accum_steps=s.accum_steps,
-                                 teacher=self.teacher, distill_alpha=t_alpha)
+                                 teacher=self.teacher, distill_alpha=t_alpha, rdrop_alpha=rdrop_alpha)
+        if rdrop_alpha > 0 and info.chief:
+            self.log(f"R-Drop: alpha {rdrop_alpha}; every batch runs twice, as 2 x the rows of one step")
         # every micro-batch of every rank is one replica of the update
         self._replicas = info.world * s.accum_steps
         # summed accuracy over replicas: a mean of per-replica ratios, or (global
@@ -270,8 +277,9 @@ class Trainer:
                 "clipped_steps": c["clipped_steps"], "skipped_steps": c["skipped_steps"]}
 
     def _label_record(self, n: float) -> Dict[str, float]:
-        """Distillation: {"label_loss": the label cross entropy of the epoch so
-        far} next to the objective the loss fields hold; {} without a teacher.
+        """Distillation and R-Drop: {"label_loss": the label cross entropy of
+        the epoch so far} next to the objective the loss fields hold; {} with
+        neither.
         n: the updates the accumulators hold."""
         la = self.step_fn.label_accum
         if la is None:

@@ -26,7 +26,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
-from tensorflow_distributed_on_gke_amd.config import check_accum_steps
+from tensorflow_distributed_on_gke_amd.config import check_accum_steps, check_rdrop
 from tensorflow_distributed_on_gke_amd.models.layers import RunCtx, WgradQueue
 from tensorflow_distributed_on_gke_amd.models.transformer import Transformer
 from tensorflow_distributed_on_gke_amd.parallel.ddp import DataParallel
@@ -78,13 +78,20 @@ class TrainStep:
     def __init__(self, model: Transformer, opt: Adam, ddp: Optional[DataParallel], workers: float,
                  seed: int = 0, dropout: Optional[float] = None, fp8_state=None,
                  defer_wgrad: Optional[bool] = None, loss_mode: str = "replica_mean",
-                 accum_steps: int = 1, teacher=None, distill_alpha: float = 0.0):
+                 accum_steps: int = 1, teacher=None, distill_alpha: float = 0.0,
+                 rdrop_alpha: float = 0.0):
         """teacher, distill_alpha: word-level distillation (train/distill.py).
         With a Teacher and distill_alpha in (0, 1] every micro-batch runs the
         teacher's forward before the student's -- inside the captured step,
         whichever way it is captured -- and trains on the mixed target; `accum`
         and `last` then hold that objective and `label_accum` the label
-        cross entropy alone."""
+        cross entropy alone.
+        rdrop_alpha: R-Drop (Transformer.loss_and_backward). With rdrop_alpha
+        > 0 every micro-batch is doubled on the device and trains on both
+        copies' label cross entropy plus rdrop_alpha / 2 times the symmetric
+        KL between them; every label count is that of both copies, `accum`
+        and `last` hold the objective and `label_accum` the label cross
+        entropy alone. 0 is the plain step. Not with fp8 or a teacher."""
         self.accum_steps = check_accum_steps(accum_steps, "fp8" if fp8_state is not None else "bf16")
         if not 0.0 <= float(distill_alpha) <= 1.0:
             raise ValueError(f"distill_alpha must lie in [0, 1], got {distill_alpha!r}")
@@ -94,6 +101,8 @@ class TrainStep:
             if fp8_state is not None:
                 raise ValueError("distillation with dtype=fp8 is not supported (use dtype=bf16)")
             self.teacher.check_student(model)
+        self.rdrop_alpha = check_rdrop(rdrop_alpha, "fp8" if fp8_state is not None else "bf16",
+                                       self.teacher is not None)
         self.model = model
         self.opt = opt
         self.ddp = ddp
@@ -162,7 +171,7 @@ class TrainStep:
         self.last = torch.zeros(2, dtype=torch.float32, device=dev)
         # distillation: the label cross entropy alone, same four slots as accum
         self.label_accum = (torch.zeros(4, dtype=torch.float32, device=dev)
-                            if self.teacher is not None else None)
+                            if self.teacher is not None or self.rdrop_alpha > 0.0 else None)
         # Variable-length batches (text data, the reference's padded-to-the-
         # batch-max shapes: english_portugese_dataset.py:44-46, __main__.py:127
         # experimental_relax_shapes): with `bucketed` set, a batch of a shape
@@ -255,7 +264,8 @@ class TrainStep:
             self.model.loss_and_backward(src, tgt, self.rt, self.workers, accum=self.accum,
                                          step_out=self.last, bump_ctr=True, ntok_sum=self._ntok_sum,
                                          ntok_total=self._ntok_total, teacher=self.teacher,
-                                         alpha=self.distill_alpha, label_accum=self.label_accum)
+                                         alpha=self.distill_alpha, label_accum=self.label_accum,
+                                         rdrop_alpha=self.rdrop_alpha)
         finally:
             self.rt.accumulate = False
             self.last_micro = True
@@ -280,6 +290,8 @@ class TrainStep:
             K.count_labels_multi(tgts, tot, K.label_total(tot.device)[1])
         else:
             tot.fill_(float(sum(int((t[:, 1:] != 0).sum()) for t in tgts)))
+        if self.rdrop_alpha > 0.0:
+            tot.mul_(2.0)  # every micro-batch runs doubled: both copies' labels
         if self._ntok_reduce is not None:
             self._ntok_reduce(tot).wait()
 
@@ -406,8 +418,9 @@ class TrainStep:
     def _cache_key(self, src_shape, tgt_shape, pos: str) -> tuple:
         """What a captured micro-batch bakes in: the batch shape, its position
         in the update, the loss divisor (world * accum_steps, or 1 with the
-        global token mean) and where the label count comes from."""
-        return (tuple(src_shape), tuple(tgt_shape), pos, self.workers, self.global_mean)
+        global token mean), where the label count comes from and the R-Drop
+        weight (0: the plain step)."""
+        return (tuple(src_shape), tuple(tgt_shape), pos, self.workers, self.global_mean, self.rdrop_alpha)
 
     def _select(self, key: tuple, src: torch.Tensor, tgt: torch.Tensor) -> None:
         """Make the captured micro-batch of this batch shape and position
