@@ -85,14 +85,34 @@ void fill_fwd(tdg::AttnArgs& a, const Tensor& out, const Tensor& lse,
   a.causal = causal;
 }
 
-void attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& out,
-              const Tensor& lse, const optional<Tensor>& kv_len, double scale, bool causal) {
+// Attention dropout (tdg_attn.h drop_*): rate p in [0, 1), p == 0 leaves the
+// argument block as without dropout; the stream is (seed, ctr, site) as for
+// the LayerNorm and embedding dropout.
+void fill_drop(tdg::AttnArgs& a, double p, int64_t seed, const optional<Tensor>& ctr, int64_t site) {
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "attention dropout: p must be in [0, 1), got ", p);
+  if (p == 0.0) return;
+  a.drop_thresh = (unsigned)std::fmin(65536.f, std::rint((float)p * 65536.f));  // tdg_common.h dropout_thresh
+  TORCH_CHECK(a.drop_thresh > 0, "attention dropout: p ", p, " rounds to no dropout");
+  a.drop_scale = (float)(1.0 / (1.0 - p));
+  a.seed = (unsigned long long)seed;
+  a.ctr = ctr_ptr(ctr);
+  a.site = (unsigned long long)site;
+}
+
+void attn_fwd_drop(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& out,
+                   const Tensor& lse, const optional<Tensor>& kv_len, double scale, bool causal,
+                   double p, int64_t seed, const optional<Tensor>& ctr, int64_t site) {
   tdg::AttnArgs a{};
   a.xcd = attn_xcd();
   fill_qkv(a, q, k, v);
   fill_fwd(a, out, lse, kv_len, scale, causal);
+  fill_drop(a, p, seed, ctr, site);
   c10::DeviceGuard g(q.device());
   check_err(tdg_attn_fwd(&a, (int)q.size(3), stream_of(q)), "tdg attn_fwd");
+}
+void attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& out,
+              const Tensor& lse, const optional<Tensor>& kv_len, double scale, bool causal) {
+  attn_fwd_drop(q, k, v, out, lse, kv_len, scale, causal, 0.0, 0, c10::nullopt, 0);
 }
 
 // Fused self-attention input projection + attention forward (L <= 128, hd
@@ -225,25 +245,34 @@ tdg::AttnArgs attn_bwd_args(const Tensor& q, const Tensor& k, const Tensor& v, c
   return a;
 }
 
+void attn_bwd_drop(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
+                   const Tensor& dout, const Tensor& lse, const Tensor& delta, const Tensor& dq,
+                   const Tensor& dk, const Tensor& dv, const optional<Tensor>& kv_len, double scale,
+                   bool causal, double p, int64_t seed, const optional<Tensor>& ctr, int64_t site) {
+  tdg::AttnArgs a = attn_bwd_args(q, k, v, o, dout, lse, delta, dq, dk, dv, kv_len, scale, causal);
+  fill_drop(a, p, seed, ctr, site);
+  c10::DeviceGuard g(q.device());
+  check_err(tdg_attn_bwd(&a, (int)q.size(3), stream_of(q)), "tdg attn_bwd");
+}
 void attn_bwd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
               const Tensor& dout, const Tensor& lse, const Tensor& delta, const Tensor& dq,
               const Tensor& dk, const Tensor& dv, const optional<Tensor>& kv_len, double scale,
               bool causal) {
-  tdg::AttnArgs a = attn_bwd_args(q, k, v, o, dout, lse, delta, dq, dk, dv, kv_len, scale, causal);
-  c10::DeviceGuard g(q.device());
-  check_err(tdg_attn_bwd(&a, (int)q.size(3), stream_of(q)), "tdg attn_bwd");
+  attn_bwd_drop(q, k, v, o, dout, lse, delta, dq, dk, dv, kv_len, scale, causal, 0.0, 0, c10::nullopt, 0);
 }
 
 // attn_bwd with the output-projection dgrad in-kernel: dO = dy2 @ wo[:, head
 // columns] per (batch, head) (dy2 [B * Lq, d], wo [d, d] bf16), never
 // written to memory. Returns false (nothing launched) when not covered
 // (Lq / Lk > 128, hd != 64).
-bool attn_bwd_fdo(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
-                  const Tensor& dy2, const Tensor& wo, const Tensor& lse, const Tensor& delta,
-                  const Tensor& dq, const Tensor& dk, const Tensor& dv,
-                  const optional<Tensor>& kv_len, double scale, bool causal) {
+bool attn_bwd_fdo_drop(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
+                       const Tensor& dy2, const Tensor& wo, const Tensor& lse, const Tensor& delta,
+                       const Tensor& dq, const Tensor& dk, const Tensor& dv,
+                       const optional<Tensor>& kv_len, double scale, bool causal, double p,
+                       int64_t seed, const optional<Tensor>& ctr, int64_t site) {
   // (o stands in for dout in the checks: the kernel computes dO itself)
   tdg::AttnArgs a = attn_bwd_args(q, k, v, o, o, lse, delta, dq, dk, dv, kv_len, scale, causal);
+  fill_drop(a, p, seed, ctr, site);
   a.dout = nullptr;
   check_bf16(dy2, "dy2");
   check_bf16(wo, "wo");
@@ -264,6 +293,14 @@ bool attn_bwd_fdo(const Tensor& q, const Tensor& k, const Tensor& v, const Tenso
   if (rc == -1) return false;
   check_err(rc, "tdg attn_bwd_fdo");
   return true;
+}
+
+bool attn_bwd_fdo(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
+                  const Tensor& dy2, const Tensor& wo, const Tensor& lse, const Tensor& delta,
+                  const Tensor& dq, const Tensor& dk, const Tensor& dv,
+                  const optional<Tensor>& kv_len, double scale, bool causal) {
+  return attn_bwd_fdo_drop(q, k, v, o, dy2, wo, lse, delta, dq, dk, dv, kv_len, scale, causal, 0.0, 0,
+                           c10::nullopt, 0);
 }
 
 // attn_bwd that also emits e5m2 copies of dQ (and of dK / dV when given),
@@ -449,7 +486,12 @@ std::vector<int64_t> attn_last_plan() {
 }  // namespace
 
 void def_attention(py::module_& m) {
+  // (attn_fwd / attn_bwd / attn_bwd_fdo: also with the trailing attention-dropout
+  // arguments p, seed, ctr, site)
   m.def("attn_fwd", &attn_fwd);
+  m.def("attn_fwd", &attn_fwd_drop);
+  m.def("attn_bwd", &attn_bwd_drop);
+  m.def("attn_bwd_fdo", &attn_bwd_fdo_drop);
   m.def("qkv_attn_fwd", &qkv_attn_fwd);
   m.def("attn_fwd_fp8", &attn_fwd_fp8);
   m.def("attn_bwd", &attn_bwd);

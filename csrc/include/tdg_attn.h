@@ -72,6 +72,16 @@ struct AttnArgs {
   const uint16_t* fdo_dy;
   const uint16_t* fdo_w;
   int fdo_d, fdo_ldy, fdo_ldw;
+  // attention dropout (the DROP kernel variants, attn_impl.h): P~ = P * keep
+  // * drop_scale with keep of element e = ((b H + h) Lq + q) Lk8 + k, Lk8 =
+  // 8 ceil(Lk / 8), drawn as tdg_common.h dropout_keep(seed, rng_offset(ctr,
+  // site), e, drop_thresh). drop_thresh = dropout_thresh(p), drop_scale =
+  // 1 / (1 - p); drop_thresh 0: off (the other four unused)
+  unsigned drop_thresh;
+  float drop_scale;
+  unsigned long long seed;
+  const long long* ctr;
+  unsigned long long site;
 };
 
 // Fused self-attention input projection + attention forward

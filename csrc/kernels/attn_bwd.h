@@ -55,7 +55,11 @@ namespace tdg {
 // ============================================================================ dK, dV
 // 4 waves, U 16-key subtiles per wave (64 U keys per workgroup): every Q / dO
 // fragment read from LDS feeds U MFMAs.
-template <int HD, int U>
+// DROP: attention dropout (attn_impl.h). Per query block each wave draws the
+// keep bits of its 16 U keys x 64 queries (key on the lane: 128 bytes of
+// bitmap per subtile, behind lse / delta), P * keep feeds dV (1 / (1 - p) in
+// its store scale) and dP * keep / (1 - p) the dS FMA.
+template <int HD, int U, bool DROP = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void attn_bwd_dkdv_kernel(AttnArgs a) {
   using T = ATile<HD>;
   constexpr int KBW = 64 * U;
@@ -64,6 +68,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
   char* ldsO = smem + T::BYTES;  // dO tile
   float* ldsL = reinterpret_cast<float*>(smem + 2 * T::BYTES);
   float* ldsD = ldsL + QB;
+  char* ldsB = smem + 2 * T::BYTES + 2 * QB * 4;  // DROP: 128 bytes per 16-key subtile
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, cl = lane & 15;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);  // (wave-uniform: scalar branches)
   int xb, h, b;
@@ -109,6 +114,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
       }
     };
     if (qstart < a.Lq) fetch_q(qstart);
+    const uint64_t doff = DROP ? drop_offset(a) : 0, bhq = ((uint64_t)b * a.H + h) * a.Lq,
+                   nb8 = (uint64_t)((a.Lk + 7) >> 3);
     for (int q0 = qstart; q0 < a.Lq; q0 += QB) {
       T::template put<256>(ldsQ, cq, tid);
       T::template put<256>(ldsO, co, tid);
@@ -118,6 +125,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
       }
       __syncthreads();
       if (q0 + QB < a.Lq) fetch_q(q0 + QB);
+      uint32_t kbits[U][4];
+      if constexpr (DROP) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+          drop_bits_key_lane(a, doff, bhq, nb8, q0, k0 + 16 * (U * w + u), ldsB + (U * w + u) * 128, g, cl,
+                             kbits[u]);
+      }
       // S[q][key] and dP[q][key]: rows q = q0 + 16t + 4g + r, col key (lane)
       short8_t pf[U][2], dsf[U][2];
 #pragma unroll
@@ -150,8 +164,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
             for (int u = 0; u < U; ++u) {
               const bool ok = TDG_ATTENDS(key[u], q, klim, a.Lq, causal);
               const float pv = masked_exp2(sv[u][r] * c - lq, ok);
-              p[tt][u][r] = pv;
-              ds[tt][u][r] = pv * (dpv[u][r] - dq);
+              if constexpr (DROP) {
+                const bool kp = drop_keep_key_lane(kbits[u], t, r);
+                p[tt][u][r] = kp ? pv : 0.f;
+                ds[tt][u][r] = pv * fmaf(dpv[u][r], kp ? a.drop_scale : 0.f, -dq);
+              } else {
+                p[tt][u][r] = pv;
+                ds[tt][u][r] = pv * (dpv[u][r] - dq);
+              }
             }
           }
         }
@@ -184,20 +204,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
     bf16_t* dvp = a.dv + b * a.dv_sb + (long long)key[u] * a.dv_sl + h * a.dv_sh;
     uint32_t lo[T::DT], hi[T::DT];
     TDG_PACK_STORE_ROW(T::DT, lo, hi, dkp, dk[u], a.scale, g, ok)
-    TDG_PACK_STORE_ROW(T::DT, lo, hi, dvp, dv[u], 1.f, g, ok)
+    TDG_PACK_STORE_ROW(T::DT, lo, hi, dvp, dv[u], DROP ? a.drop_scale : 1.f, g, ok)
   }
 }
 
 // ============================================================================ dQ
 // 4 waves, U 16-query subtiles per wave (64 U queries per workgroup): every
 // K / V fragment read from LDS feeds U MFMAs.
-template <int HD, int U>
+// DROP: attention dropout (attn_impl.h), the forward's scheme: per key tile
+// each wave draws the keep bits of its 16 U query rows x 64 keys (128 bytes
+// of bitmap per subtile behind the K / V images).
+template <int HD, int U, bool DROP = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void attn_bwd_dq_kernel(AttnArgs a) {
   using T = ATile<HD>;
   constexpr int QBW = 64 * U;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ldsK = smem;
   char* ldsV = smem + T::BYTES;
+  char* ldsB = smem + 2 * T::BYTES;  // DROP: 128 bytes per 16-query subtile
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, cl = lane & 15;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);  // (wave-uniform: scalar branches)
   int xb, h, b;
@@ -251,6 +275,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
     T::template fetch<256>(ck, kb, a.k_sl, 0, a.Lk, tid);
     T::template fetch<256>(cv, vb, a.v_sl, 0, a.Lk, tid);
   }
+  uint64_t doff = 0, rowblk[U];
+  if constexpr (DROP) {
+    doff = drop_offset(a);
+#pragma unroll
+    for (int u = 0; u < U; ++u) rowblk[u] = drop_row_block(a, b, h, qrow[u]);
+  }
   for (int k0 = 0; k0 < klim; k0 += KB) {
     T::template put<256>(ldsK, ck, tid);
     T::template put<256>(ldsV, cv, tid);
@@ -258,6 +288,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
     if (k0 + KB < klim) {
       T::template fetch<256>(ck, kb, a.k_sl, k0 + KB, a.Lk, tid);
       T::template fetch<256>(cv, vb, a.v_sl, k0 + KB, a.Lk, tid);
+    }
+    uint32_t kbits[U][2];
+    if constexpr (DROP) {
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        drop_bits_query_lane<KB>(a, doff, rowblk[u], k0, ldsB + (U * w + u) * 128, g, cl, kbits[u]);
     }
     short8_t dsf[U][2];
 #pragma unroll
@@ -280,7 +316,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
           }
         }
         // (every tile takes the masked branch)
-        TDG_DS_QUERY_LANE(U, false, sv, dpv, L, D, c, qrow, k0 + 16 * t + 4 * g, klim, a.Lq, causal, ds[tt])
+        if constexpr (DROP) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int key = k0 + 16 * t + 4 * g + r;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+              const bool ok = TDG_ATTENDS(key, qrow[u], klim, a.Lq, causal);
+              const float pv = masked_exp2(sv[u][r] * c - L[u], ok);
+              const float ksc = drop_keep_query_lane(kbits[u], t, r) ? a.drop_scale : 0.f;
+              ds[tt][u][r] = pv * fmaf(dpv[u][r], ksc, -D[u]);
+            }
+          }
+        } else {
+          TDG_DS_QUERY_LANE(U, false, sv, dpv, L, D, c, qrow, k0 + 16 * t + 4 * g, klim, a.Lq, causal, ds[tt])
+        }
       }
 #pragma unroll
       for (int u = 0; u < U; ++u)
@@ -913,7 +963,10 @@ __device__ __forceinline__ void fdo_tile(const AttnArgs& a, int b, int h, char* 
     }                                                                                                     \
   }
 
-template <int HD, int U, bool FDO = false>
+// DROP: attention dropout (attn_impl.h) in phase 1, as in attn_bwd_dkdv_kernel:
+// per 64 queries each wave draws the keep bits of its 16 U keys (128 bytes of
+// bitmap per subtile behind lse / delta); phase 2 reads the finished dS.
+template <int HD, int U, bool FDO = false, bool DROP = false>
 __global__ __launch_bounds__(512 / U) __attribute__((amdgpu_waves_per_eu(U == 1 ? (HD <= 64 ? 4 : 2) : 2))) void attn_bwd_fused_kernel(AttnArgs a) {
   static_assert(!FDO || (HD == 64 && U == 1), "in-kernel dO: hd 64, 8 waves");
   using T = ATile<HD>;
@@ -1033,8 +1086,21 @@ __global__ __launch_bounds__(512 / U) __attribute__((amdgpu_waves_per_eu(U == 1 
   uint32_t pk[U][8][2], dk2[U][8][2];
   const bool active = 16 * U * w < klim;  // wave-uniform
   if (active) {
+    char* ldsB = reinterpret_cast<char*>(ldsD + R);  // DROP: 128 bytes per 16-key subtile
+    const uint64_t doff = DROP ? drop_offset(a) : 0, bhq = ((uint64_t)b * a.H + h) * a.Lq,
+                   nb8 = (uint64_t)((a.Lk + 7) >> 3);
+    uint32_t kbits[U][4];
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
+      if constexpr (DROP) {
+        // (uniform: some query of the 64 from 16 t on attends to the wave's keys)
+        if ((t & 3) == 0 && 16 * t < a.Lq && (!causal || 16 * t + 63 >= 16 * U * w)) {
+#pragma unroll
+          for (int u = 0; u < U; ++u)
+            drop_bits_key_lane(a, doff, bhq, nb8, 16 * t, 16 * (U * w + u), ldsB + (U * w + u) * 128, g, cl,
+                               kbits[u]);
+        }
+      }
       const bool live = 16 * t < a.Lq && (!causal || 16 * t + 15 >= 16 * U * w);  // uniform
       if (!live) {  // (no query of the tile attends to the wave's keys: P = dS = 0)
 #pragma unroll
@@ -1079,6 +1145,14 @@ __global__ __launch_bounds__(512 / U) __attribute__((amdgpu_waves_per_eu(U == 1 
             const bool ok = TDG_ATTENDS(key[u], q, klim, a.Lq, causal);
             pv[r] = masked_exp2(sv[u][r] * c - l4[r], ok);
             dv4[r] = pv[r] * (dpv[u][r] - d4[r]);
+          }
+        }
+        if constexpr (DROP) {  // (after either branch: dS on the undropped P, then P * keep)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const bool kp = drop_keep_key_lane(kbits[u], t & 3, r);
+            dv4[r] = pv[r] * fmaf(dpv[u][r], kp ? a.drop_scale : 0.f, -d4[r]);
+            pv[r] = kp ? pv[r] : 0.f;
           }
         }
         pk[u][t][0] = pack2bf(pv[0], pv[1]);
@@ -1132,7 +1206,7 @@ __global__ __launch_bounds__(512 / U) __attribute__((amdgpu_waves_per_eu(U == 1 
     bf16_t* dvp = a.dv + b * a.dv_sb + (long long)key[u] * a.dv_sl + h * a.dv_sh;
     uint32_t lo[T::DT], hi[T::DT];
     TDG_PACK_STORE_ROW(T::DT, lo, hi, dkp, dk[u], sc, g, ok)
-    TDG_PACK_STORE_ROW(T::DT, lo, hi, dvp, dv[u], 1.f, g, ok)
+    TDG_PACK_STORE_ROW(T::DT, lo, hi, dvp, dv[u], DROP ? a.drop_scale : 1.f, g, ok)
   }
   __syncthreads();
   TDG_STAMP(6);
@@ -1181,6 +1255,7 @@ constexpr int fused_bwd_lds() {
   constexpr int TB = 128 * HD * 2, SB = 128 * 256;
   return (2 * TB >= SB ? 3 * TB : 3 * TB + SB) + 2 * 128 * 4;
 }
+constexpr int FUSED_DROP_LDS = 8 * 128;  // DROP: 128 bytes of keep bits per 16-key subtile
 }  // namespace
 
 // Fused backward with the output-projection dgrad in-kernel (FDO): Lq, Lk <=
@@ -1191,8 +1266,15 @@ extern "C" int tdg_attn_bwd_fdo(const AttnArgs* ap, hipStream_t st) {
       a.fdo_ldw % 8 || !a.fdo_dy || !a.fdo_w)
     return -1;
   constexpr int lds = fused_bwd_lds<64>() > FDO_STAGES * FDO_SB ? fused_bwd_lds<64>() : FDO_STAGES * FDO_SB;
-  big_lds<attn_bwd_fused_kernel<64, 1, true>>();
+  // (the DROP keep bits lie at fused_bwd_lds<64>(), inside the dO stages)
+  static_assert(fused_bwd_lds<64>() + FUSED_DROP_LDS <= lds, "keep bits inside the FDO stages");
   attn_plan_record(ATTN_BWD_FDO, 64, (long long)a.B * a.H, 512);
+  if (a.drop_thresh) {
+    big_lds<attn_bwd_fused_kernel<64, 1, true, true>>();
+    hipLaunchKernelGGL((attn_bwd_fused_kernel<64, 1, true, true>), dim3(a.B * a.H), dim3(512), lds, st, a);
+    return 0;
+  }
+  big_lds<attn_bwd_fused_kernel<64, 1, true>>();
   hipLaunchKernelGGL((attn_bwd_fused_kernel<64, 1, true>), dim3(a.B * a.H), dim3(512), lds, st, a);
   return 0;
 }
@@ -1206,9 +1288,26 @@ int bwd_hd(const AttnArgs& a, hipStream_t st) {
     // read feeding two MFMAs, 231 VGPRs) measured slower: 22.7 vs 21.7 us per
     // call, step 5.15 vs 5.13 ms (profiles/r3s2/attn_bwd_u2.txt)
     constexpr int U = 1;
-    big_lds<attn_bwd_fused_kernel<HD, U>>();
     attn_plan_record(ATTN_BWD_FUSED, HD, (long long)a.B * a.H, 512 / U);
+    if (a.drop_thresh) {
+      big_lds<attn_bwd_fused_kernel<HD, U, false, true>>();
+      hipLaunchKernelGGL((attn_bwd_fused_kernel<HD, U, false, true>), dim3(a.B * a.H), dim3(512 / U),
+                         lds + FUSED_DROP_LDS, st, a);
+      return 0;
+    }
+    big_lds<attn_bwd_fused_kernel<HD, U>>();
     hipLaunchKernelGGL((attn_bwd_fused_kernel<HD, U>), dim3(a.B * a.H), dim3(512 / U), lds, st, a);
+    return 0;
+  }
+  // attention dropout: the register-staged pair at every head dim (the
+  // pipelined hd-64 kernels have no DROP variant), 512 bytes of keep bits each
+  if (a.drop_thresh) {
+    attn_plan_record(ATTN_BWD_SPLIT, HD, (long long)cdiv(a.Lq, QB) * a.H * a.B, 256,
+                     (long long)cdiv(a.Lk, KB) * a.H * a.B);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, 1, true>), dim3(cdiv(a.Lq, QB), a.H, a.B), dim3(256),
+                       2 * ATile<HD>::BYTES + 512, st, a);
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<HD, 1, true>), dim3(cdiv(a.Lk, KB), a.H, a.B), dim3(256),
+                       2 * ATile<HD>::BYTES + 2 * QB * 4 + 512, st, a);
     return 0;
   }
   // dQ first: it also writes delta = rowsum(dO * O), which dK/dV reads

@@ -14,7 +14,12 @@ namespace tdg {
 // rate (1 KiB per 16-cycle MFMA per wave), U = 2 halves them.
 // KT keys per LDS tile (64 or 128: one load phase and one barrier pair for a
 // whole <= 128-key sequence).
-template <int HD, int NWV, int KT, int U>
+// DROP: attention dropout (attn_impl.h). Each wave draws the keep bits of its
+// own 16 U query rows x KT keys behind the staging barrier, next to the next
+// tile's loads, into its part of a bitmap behind the K / V images (16 U KT / 8
+// bytes per wave); l sums the undropped P, the dropped P feeds the PV MFMAs
+// and 1 / (1 - p) scales O once at the end.
+template <int HD, int NWV, int KT, int U, bool DROP = false>
 __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(2))) void attn_fwd_kernel(AttnArgs a) {
   using T = ATile<HD>;
   constexpr int QBW = 16 * NWV * U;
@@ -70,6 +75,13 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(2))) v
       T::template fetch<NWV * 64>(cv[h64], vb, a.v_sl, kk0 + 64 * h64, a.Lk, tid);
     }
   };
+  char* ldsB = smem + 2 * (KT / 64) * T::BYTES + w * (16 * U * (KT / 8));  // DROP: the wave's keep bits
+  uint64_t doff = 0, rowblk[U];
+  if constexpr (DROP) {
+    doff = drop_offset(a);
+#pragma unroll
+    for (int u = 0; u < U; ++u) rowblk[u] = drop_row_block(a, b, h, qrow[u]);
+  }
   if (klim > 0) fetch_kv(0);
   for (int k0 = 0; k0 < klim; k0 += KT) {
 #pragma unroll
@@ -80,6 +92,12 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(2))) v
     __syncthreads();
     if (k0 == 0) TDG_STAMP(1);
     if (k0 + KT < klim) fetch_kv(k0 + KT);
+    uint32_t kbits[U][KT / 32];
+    if constexpr (DROP) {
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        drop_bits_query_lane<KT>(a, doff, rowblk[u], k0, ldsB + u * 16 * (KT / 8), g, cl, kbits[u]);
+    }
     f32x4 s[U][NT16];
 #pragma unroll
     for (int t = 0; t < NT16; ++t) {
@@ -94,9 +112,16 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(2))) v
     }
     short8_t pf[U][NT16 / 2];
 #pragma unroll
-    for (int u = 0; u < U; ++u)
-      softmax_tile<NT16, T::DT>(s[u], m[u], l[u], oacc[u], pf[u], tile_masked(k0, KTILE, klim, causal, wq0),
-                                k0, klim, causal, qrow[u], g, c);
+    for (int u = 0; u < U; ++u) {
+      if constexpr (DROP) {
+        const bool msk = tile_masked(k0, KTILE, klim, causal, wq0);
+        softmax_max<NT16, T::DT>(s[u], m[u], l[u], oacc[u], msk, k0, klim, causal, qrow[u], g, c);
+        softmax_exp<NT16, true>(s[u], m[u], l[u], pf[u], msk ? 1.f : c, kbits[u]);
+      } else {
+        softmax_tile<NT16, T::DT>(s[u], m[u], l[u], oacc[u], pf[u], tile_masked(k0, KTILE, klim, causal, wq0),
+                                  k0, klim, causal, qrow[u], g, c);
+      }
+    }
 #pragma unroll
     for (int s2 = 0; s2 < NT16 / 2; ++s2) {
 #pragma unroll
@@ -109,6 +134,12 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(2))) v
     __syncthreads();
   }
   TDG_STAMP(2);
+  if constexpr (DROP) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int dt = 0; dt < T::DT; ++dt) oacc[u][dt] *= a.drop_scale;
+  }
 #pragma unroll
   for (int u = 0; u < U; ++u) TDG_FWD_FINISH(T::DT, a, b, h, qrow[u], oacc[u], m[u], l[u], g)
 #ifdef TDG_STAMPS
@@ -298,8 +329,35 @@ __global__ void attn_probs_kernel(AttnArgs a, float* __restrict__ probs) {
 using namespace tdg;
 
 namespace {
+// The register-staged forward with attention dropout: the three launch shapes
+// of fwd_hd below, each with its waves' keep-bit bitmap behind the K / V
+// images; hd 64 with Lq > 128 too (the grid covers any Lq), where the
+// pipelined kernel has no DROP variant.
+template <int HD>
+int fwd_drop_hd(const AttnArgs& a, hipStream_t st) {
+  if (a.Lq > 64) {
+    dim3 grid(cdiv(a.Lq, 128), a.H, a.B);
+    constexpr int lds = 4 * ATile<HD>::BYTES + 128 * 16;
+    attn_plan_record(HD <= 64 ? ATTN_FWD128 : ATTN_FWD128W8, HD, (long long)grid.x * grid.y * grid.z,
+                     HD <= 64 ? 256 : 512);
+    if constexpr (HD <= 64) {
+      big_lds<attn_fwd_kernel<HD, 4, 128, 2, true>>();
+      hipLaunchKernelGGL((attn_fwd_kernel<HD, 4, 128, 2, true>), grid, dim3(256), lds, st, a);
+    } else {
+      big_lds<attn_fwd_kernel<HD, 8, 128, 1, true>>();
+      hipLaunchKernelGGL((attn_fwd_kernel<HD, 8, 128, 1, true>), grid, dim3(512), lds, st, a);
+    }
+  } else {
+    dim3 grid(cdiv(a.Lq, 64), a.H, a.B);
+    attn_plan_record(ATTN_FWD64, HD, (long long)grid.x * grid.y * grid.z, 256);
+    hipLaunchKernelGGL((attn_fwd_kernel<HD, 4, 64, 1, true>), grid, dim3(256), 2 * ATile<HD>::BYTES + 64 * 8,
+                       st, a);
+  }
+  return 0;
+}
 template <int HD>
 int fwd_hd(const AttnArgs& a, hipStream_t st) {
+  if (a.drop_thresh) return fwd_drop_hd<HD>(a, st);
   // (64 queries per workgroup for Lq > 64 -- twice the workgroups, K / V
   // staged by both halves -- measured 17.2 vs 12.2 us at B 64, H 8, L 128:
   // csrc/lab/attn_lab.cpp, profiles/attn_lab/)

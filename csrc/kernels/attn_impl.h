@@ -279,6 +279,111 @@ __device__ __forceinline__ short8_t gfrag(const bf16_t* __restrict__ rowp, bool 
   }
 }
 
+// ============================================================================ attention dropout
+// The DROP variants of attn_fwd_kernel, attn_bwd_fused_kernel (plain and
+// FDO), attn_bwd_dq_kernel and attn_bwd_dkdv_kernel (bf16; AttnArgs
+// drop_thresh != 0). Semantics, per (batch b, head h, query q, key k):
+//   P = softmax(S) over the attended keys and lse, as without dropout;
+//   P~ = P * keep / (1 - p), O = P~ V;
+//   dV = P~^T dO, dP = (dO V^T) * keep / (1 - p), delta = rowsum(dO * O)
+//   (unchanged: sum_k P dP = sum_k P~ dP~), dS = P (dP - delta), dQ / dK as
+//   without dropout.
+// keep is dropout_keep (tdg_common.h) of element e = ((b H + h) Lq + q) Lk8 +
+// k of the stream (seed, rng_offset(ctr, site)), Lk8 = 8 ceil(Lk / 8): the
+// keys 8j .. 8j + 7 of a query row are the 8 half-word draws of ONE Philox
+// call, block ((b H + h) Lq + q) Lk8 / 8 + j. It depends on the absolute
+// (b, h, q, k) alone, not on kernel, tile or workgroup; a kv_len = 0 row is
+// dropped like any other. ops/philox.py keep_mask(seed, offset, B H Lq Lk8, p)
+// viewed [B, H, Lq, Lk8] and cut to Lk is the same mask.
+//
+// No lane's accumulator elements cover an 8-key block (query on the lane: 4
+// keys of each 16; key on the lane: one key of 16 queries), so a lane that
+// drew its own elements would run 4 to 16 Philox calls per 16 x 16 tile and
+// use an eighth to a half of each. Instead the WAVE draws the bits of its own
+// 16-row subtile, each lane whole blocks that no other lane draws (every draw
+// used: 2 calls per lane for 16 rows x 64 keys), the lanes exchange them
+// through a wave-private LDS bitmap (128 B per 16 x 64 subtile; one narrow
+// store and one 8- / 16-byte read per lane) and apply them as selects on the
+// P / dP registers. No workgroup barrier: a wave reads only what it wrote, and
+// a wave's LDS operations complete in order. 1 / (1 - p) costs nothing per
+// element: it rides on the forward's final 1 / l and the backward's dV store
+// scale, and on the select that feeds the dP FMA.
+__device__ __forceinline__ void wave_lds_sync() {  // this wave's LDS stores before its LDS loads
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ uint64_t drop_offset(const AttnArgs& a) { return rng_offset(a.ctr, a.site); }
+// 8-key blocks per query row, and the first block of row q of (b, h)
+__device__ __forceinline__ uint64_t drop_row_block(const AttnArgs& a, int b, int h, int q) {
+  return (((uint64_t)b * a.H + h) * a.Lq + q) * (uint64_t)((a.Lk + 7) >> 3);
+}
+// Query on the lane (forward, dQ: lane (g, cl) = row cl of a 16-query
+// subtile, keys 16 t + 4 g + r of the KT-key tile at k0): bits[] = the row's
+// keep bits shifted by 4 g, so that key (t, r) is bit 16 (t & 1) + r of word
+// t >> 1. rowblk: drop_row_block of the lane's row. bm: the subtile's bitmap,
+// 16 rows x KT / 8 bytes; lane g draws bytes g KT / 32 .. of its row. (Blocks
+// past the row's last belong to the next row: those keys are >= Lk, masked.)
+template <int KT>
+__device__ __forceinline__ void drop_bits_query_lane(const AttnArgs& a, uint64_t off, uint64_t rowblk,
+                                                     int k0, char* bm, int g, int cl,
+                                                     uint32_t (&bits)[KT / 32]) {
+  constexpr int NB = KT / 8, PER = NB / 4;
+  uint32_t mine = 0;
+#pragma unroll
+  for (int i = 0; i < PER; ++i)
+    mine |= dropout_keep_run<8>(a.seed, off, (rowblk + (uint64_t)((k0 >> 3) + g * PER + i)) << 3,
+                                a.drop_thresh) << (8 * i);
+  if constexpr (KT == 64) {
+    *reinterpret_cast<uint16_t*>(bm + cl * NB + 2 * g) = (uint16_t)mine;
+    wave_lds_sync();
+    const uint2 r = *reinterpret_cast<const uint2*>(bm + cl * NB);
+    bits[0] = r.x >> (4 * g);
+    bits[1] = r.y >> (4 * g);
+  } else {
+    static_assert(KT == 128, "64- or 128-key tiles");
+    *reinterpret_cast<uint32_t*>(bm + cl * NB + 4 * g) = mine;
+    wave_lds_sync();
+    const uint4 r = *reinterpret_cast<const uint4*>(bm + cl * NB);
+    bits[0] = r.x >> (4 * g);
+    bits[1] = r.y >> (4 * g);
+    bits[2] = r.z >> (4 * g);
+    bits[3] = r.w >> (4 * g);
+  }
+  wave_lds_sync();  // (the next tile's stores stay behind these loads)
+}
+__device__ __forceinline__ bool drop_keep_query_lane(const uint32_t* bits, int t, int r) {
+  return (bits[t >> 1] >> (16 * (t & 1) + r)) & 1u;
+}
+// Key on the lane (dK/dV, the fused backward's phase 1: lane (g, cl) = key
+// kb0 + cl of a 16-key subtile, queries q0 + 16 t + 4 g + r, t < 4): bits[t]
+// byte r bit 0 = keep(query (t, r), the lane's key). bhq = (b H + h) Lq, nb8 =
+// 8-key blocks per row, kb0 a multiple of 16. bm: 128 bytes, [key half][g][4 t
+// + r]; lane (g, cl) draws the blocks of queries 4 t + r = 2 (cl & 7), + 1 in
+// key half cl >> 3. (Queries >= Lq draw a later row's blocks: masked.)
+__device__ __forceinline__ void drop_bits_key_lane(const AttnArgs& a, uint64_t off, uint64_t bhq,
+                                                   uint64_t nb8, int q0, int kb0, char* bm, int g,
+                                                   int cl, uint32_t (&bits)[4]) {
+  const int hh = cl >> 3, idx = cl & 7;
+  uint32_t mine = 0;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int q = q0 + 16 * (idx >> 1) + 4 * g + 2 * (idx & 1) + i;
+    const uint64_t blk = (bhq + (uint64_t)q) * nb8 + (uint64_t)((kb0 >> 3) + hh);
+    mine |= dropout_keep_run<8>(a.seed, off, blk << 3, a.drop_thresh) << (8 * i);
+  }
+  *reinterpret_cast<uint16_t*>(bm + hh * 64 + g * 16 + 2 * idx) = (uint16_t)mine;
+  wave_lds_sync();
+  const uint4 r = *reinterpret_cast<const uint4*>(bm + hh * 64 + g * 16);
+  bits[0] = r.x >> idx;
+  bits[1] = r.y >> idx;
+  bits[2] = r.z >> idx;
+  bits[3] = r.w >> idx;
+  wave_lds_sync();
+}
+__device__ __forceinline__ bool drop_keep_key_lane(const uint32_t* bits, int t, int r) {
+  return (bits[t] >> (8 * r)) & 1u;
+}
 
 // One key tile of the online softmax for the lane's query row (swapped
 // QK^T: s[t][r] = S[key = k0 + 16t + 4g + r][row], raw logits). m is the
@@ -338,9 +443,12 @@ __device__ __forceinline__ void softmax_max(f32x4 (&s)[NT16], float& m, float& l
   }
 }
 // cs: c for a raw (unmasked) tile, 1 for a masked (already scaled) one
-template <int NT16>
+// DROP: bits = the row's keep bits (drop_bits_query_lane); l sums the
+// undropped P, the packed operand is P * keep
+template <int NT16, bool DROP = false>
 __device__ __forceinline__ void softmax_exp(f32x4 (&s)[NT16], float m, float& l,
-                                            short8_t (&pf)[NT16 / 2], float cs) {
+                                            short8_t (&pf)[NT16 / 2], float cs,
+                                            const uint32_t* bits = nullptr) {
   const float nm = m == -INFINITY ? 0.f : -m;  // all masked so far: exp2(-inf) = 0, no NaN
   float rs = 0.f;
 #pragma unroll
@@ -348,8 +456,9 @@ __device__ __forceinline__ void softmax_exp(f32x4 (&s)[NT16], float m, float& l,
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float p = fast_exp2(fmaf(s[t][r], cs, nm));
-      s[t][r] = p;
       rs += p;
+      if constexpr (DROP) s[t][r] = drop_keep_query_lane(bits, t, r) ? p : 0.f;
+      else s[t][r] = p;
     }
   l += rs;
 #pragma unroll

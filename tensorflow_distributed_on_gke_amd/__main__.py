@@ -25,7 +25,9 @@ torch.distributed.run (RANK set) or with one process. With `--set
 distill_teacher=PREFIX[,PREFIX...]` the model is a student trained on the
 next-token distributions of those frozen models (train/distill.py). With
 `--set rdrop_alpha=5` it trains with R-Drop: every batch twice under two
-dropout masks, the two next-token distributions pulled together.
+dropout masks, the two next-token distributions pulled together. With `--set
+attention_dropout=0.1` the attention probabilities are dropped too, inside
+the attention kernels.
 `test` is the reference's test.py + Tester (greedy translation, or beam
 search with --beam N --length-penalty ALPHA, or --sample N translations drawn
 per sentence); with --input / --output it translates a file, one sentence per

@@ -158,6 +158,12 @@ class Settings:
     # Finite and >= 0; not with dtype=fp8 or a distillation teacher.
     # Validation stays the plain one
     rdrop_alpha: float = 0.0
+    # extension, off at 0: dropout on the attention probabilities (fairseq
+    # --attention-dropout, tensor2tensor attention_dropout), drawn inside the
+    # attention kernels from Philox sites of its own beside `dropout`'s. In
+    # [0, 1); > 0 not with dtype=fp8. Training only: validation, scoring and
+    # decoding never drop
+    attention_dropout: float = 0.0
 
     def global_batch(self, world: int) -> int:
         return self.local_batch_size * world
@@ -206,6 +212,7 @@ def load_settings(path: Optional[str] = None, overrides: Optional[List[str]] = N
     check_batch_tokens(s.batch_tokens, s.data, s.length_bucket)
     check_distill(s.distill_teacher, s.distill_weights, s.distill_alpha, s.dtype)
     check_rdrop(s.rdrop_alpha, s.dtype, bool(s.distill_teacher))
+    check_attention_dropout(s.attention_dropout, s.dtype)
     return s
 
 
@@ -294,3 +301,14 @@ def check_rdrop(alpha: Any, dtype: str = "bf16", teacher: bool = False) -> float
         raise ValueError(f"rdrop_alpha={alpha} together with distill_teacher is not supported: "
                          "one objective beside the label cross entropy at a time")
     return float(alpha)
+
+
+def check_attention_dropout(p: Any, dtype: str = "bf16") -> float:
+    """attention_dropout is a finite number in [0, 1) (0: off); > 0 is refused
+    with dtype=fp8. ValueError otherwise."""
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= float(p) < 1.0:
+        raise ValueError(f"attention_dropout must be a number in [0, 1) (0: off), got {p!r}")
+    if p > 0 and dtype == "fp8":
+        raise ValueError(f"attention_dropout={p} with dtype=fp8 is not supported: the fp8 attention "
+                         "kernels have no dropout variant (use dtype=bf16)")
+    return float(p)

@@ -55,7 +55,7 @@ from tensorflow_distributed_on_gke_amd.models.wgrad import (  # noqa: F401 (Wgra
     WgradQueue, _beta, _fold_bias_later, _fp8_grad_bias, _ready, _wgrad)
 from tensorflow_distributed_on_gke_amd.ops import kernels as K
 from tensorflow_distributed_on_gke_amd.ops import fp8, philox
-from tensorflow_distributed_on_gke_amd.ops.kernels.attention import _ref_attn_fwd
+from tensorflow_distributed_on_gke_amd.ops.kernels.attention import _ref_attn_fwd, attn_keep_scale
 
 LN_EPS = 1e-6
 
@@ -79,10 +79,16 @@ class RunCtx:
     # {embedding site: ops.kernels.EmbCsr}: the token sorts of this forward's
     # embedding backwards (one launch for both tables, Transformer.features)
     emb_csr: Optional[dict] = None
+    # dropout rate on the attention probabilities (training only; bf16)
+    attn_dropout: float = 0.0
 
     @property
     def p(self) -> float:
         return self.dropout if self.training else 0.0
+
+    @property
+    def attn_p(self) -> float:
+        return self.attn_dropout if self.training else 0.0
 
     def cpu_offset(self, site: int) -> int:
         if self.ctr is None:
@@ -296,9 +302,12 @@ class EmbedFn(torch.autograd.Function):
 
 # =============================================================================== attention (CPU reference core)
 # (the forward, _ref_attn_fwd, lives next to the kernel it stands in for: ops/kernels/attention.py)
-def _ref_attn_bwd(q, k, v, p, dout, scale):
-    dv = torch.einsum("bhqk,bqhd->bkhd", p, dout)
-    dp = torch.einsum("bqhd,bkhd->bhqk", dout, v)
+def _ref_attn_bwd(q, k, v, p, dout, scale, keep_scale=None):
+    """keep_scale: the forward's attention-dropout multiplier (p stays the
+    undropped softmax): dV from p * keep_scale, dP masked and scaled alike."""
+    ks = 1.0 if keep_scale is None else keep_scale.to(p.dtype)
+    dv = torch.einsum("bhqk,bqhd->bkhd", p * ks, dout)
+    dp = torch.einsum("bqhd,bkhd->bhqk", dout, v) * ks
     ds = p * (dp - (dp * p).sum(-1, keepdim=True))
     dq = torch.einsum("bhqk,bkhd->bqhd", ds, k) * scale
     dk = torch.einsum("bhqk,bqhd->bkhd", ds, q) * scale
@@ -363,6 +372,10 @@ def _lean_bwd_end(lb: _LeanBwd, g8, w_in: Param, wo: Param, rt: RunCtx) -> None:
 _ExtKV = namedtuple("_ExtKV", "kv kv8 kvs g g8 gk part cs_k cs_v",
                     defaults=((None, None), (None, None), None, None, 0, 0))
 
+# an attention block's dropout on its probabilities draws from a site of its own: this plus the
+# block's LayerNorm site (Transformer's sites stay below 64; rng_offset has 4096 per counter step)
+ATTN_DROP_SITE = 2048
+
 
 def _layer_kv(t, layer: int, d: int, heads: int):
     """Decoder layer `layer`'s (K, V) [B, S, H, hd] views of a batched [B, S, layers * 2d]
@@ -402,6 +415,13 @@ def _attn_block_fwd(ctx, x, w_in: Param, b_in: Param, wo: Param, bo: Param, gamm
     kx = [] if lean else None
     ctx.q8 = o8e = None
     kv, kv8 = (ext.kv, ext.kv8) if ext is not None else (None, None)
+    # attention dropout (training, bf16): the register-staged attention kernels' DROP variants,
+    # so no fused projection + attention; the backward regenerates the mask from ctx.drop
+    ctx.drop = drop = ((rt.attn_p, rt.seed, rt.ctr, ATTN_DROP_SITE + site) if rt.attn_p > 0 else None)
+    ctx.attn_ks = None
+    if drop is not None and rt.fp8 is not None:
+        raise RuntimeError("attention dropout with fp8 is not supported: the fp8 attention kernels "
+                           "have no dropout variant")
     if x.is_cuda:
         Lk = L if ext is None else (kv8 if kv[0] is None else kv)[0].shape[1]
         f8 = (rt.fp8 is not None and (ext is None or kv8[0] is not None)
@@ -415,7 +435,7 @@ def _attn_block_fwd(ctx, x, w_in: Param, b_in: Param, wo: Param, bo: Param, gamm
              if rt.fp8 is not None else None)
         proj, proj8 = (r[0], r[1]) if f8 and r is not None else (r, None)
         fused = None
-        if proj is None and not f8b and rt.fp8 is None and rt.attn_maps is None:
+        if proj is None and not f8b and rt.fp8 is None and rt.attn_maps is None and drop is None:
             # projection + attention forward in one launch (<= 128 tokens)
             fused = K.qkv_attn_fwd(x2, w_in.compute, b_in.master, B, heads, kv_len, scale, causal,
                                    *(kv or ()))
@@ -436,11 +456,14 @@ def _attn_block_fwd(ctx, x, w_in: Param, b_in: Param, wo: Param, bo: Param, gamm
             o, aux = K.attn_fwd_fp8(*_qkv(proj8, kv8, B, heads, hd), sq, skv, skv, kv_len, scale,
                                     causal, *(o8e or ()))
         else:
-            o, aux = K.attn_fwd(q, k, v, kv_len, scale, causal)
+            o, aux = K.attn_fwd(q, k, v, kv_len, scale, causal, drop=drop)
     else:
         proj = x2 @ w_in.master.t() + b_in.master
         q, k, v = _qkv(proj, kv, B, heads, hd)
-        o, aux = _ref_attn_fwd(q, k, v, kv_len, causal, scale)
+        if drop is not None:  # (CPU reference: the same mask, kept for the backward)
+            ctx.attn_ks = attn_keep_scale(drop[0], rt.seed, rt.cpu_offset(drop[3]), B, heads, L,
+                                          k.shape[1])
+        o, aux = _ref_attn_fwd(q, k, v, kv_len, causal, scale, ctx.attn_ks)
     if rt.attn_maps is not None:  # (_f8_bwd_planned: the bf16 q, k exist when maps are asked for)
         rt.attn_maps[site] = attention_probs(q, k, kv_len, causal, scale)
     y = _attn_out_ln_fwd(ctx, o, x, wo, bo, gamma, beta, site, rt, kx, o8e)
@@ -521,16 +544,19 @@ def _attn_block_bwd(ctx, dy, x2, proj, o, aux, kv_len, ext: Optional[_ExtKV] = N
         dq, dk, dv = _qkv(g, gkv, B, heads, hd)
         # (<= 128 tokens: the output projection's dgrad dO = ds @ Wo inside the attention
         # backward)
-        if not K.attn_bwd_fdo(q, k, v, o, ds2, wo.compute, aux, dq, dk, dv, kv_len, scale, causal):
+        if not K.attn_bwd_fdo(q, k, v, o, ds2, wo.compute, aux, dq, dk, dv, kv_len, scale, causal,
+                              drop=ctx.drop):
             do = K.linear_dgrad(ds2, wo.compute, d)
-            K.attn_bwd(q, k, v, o, do.view(B, L, heads, hd), aux, dq, dk, dv, kv_len, scale, causal)
+            K.attn_bwd(q, k, v, o, do.view(B, L, heads, hd), aux, dq, dk, dv, kv_len, scale, causal,
+                       drop=ctx.drop)
         _wgrad(rt, g, x2, N, w_in, b_in)
     else:
         _write_grad(wo, ds2.t() @ o.reshape(M, d), rt)
         _ready(rt, wo)
         do = (ds2 @ wo.master).view(B, L, heads, hd)
         g = torch.empty(M, N, dtype=ds2.dtype)
-        for dst, src in zip(_qkv(g, gkv, B, heads, hd), _ref_attn_bwd(q, k, v, aux, do, scale)):
+        for dst, src in zip(_qkv(g, gkv, B, heads, hd),
+                            _ref_attn_bwd(q, k, v, aux, do, scale, ctx.attn_ks)):
             dst.copy_(src)
         _write_grad(w_in, g.t() @ x2, rt)
         _write_grad(b_in, g.sum(0), rt)

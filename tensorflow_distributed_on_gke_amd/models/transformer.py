@@ -43,6 +43,9 @@ class ModelConfig:
     max_tgt_len: int = 1000
     dropout: float = 0.1
     label_smoothing: float = 0.0
+    # dropout on the attention probabilities of every attention block
+    # (training; config.check_attention_dropout). 0: off
+    attention_dropout: float = 0.0
 
     def to_dict(self) -> dict:
         return asdict(self)

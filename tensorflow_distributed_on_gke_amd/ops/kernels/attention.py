@@ -7,13 +7,34 @@ from typing import Optional
 
 import torch
 
+from tensorflow_distributed_on_gke_amd.ops import philox
 from tensorflow_distributed_on_gke_amd.ops._ext import C
 from tensorflow_distributed_on_gke_amd.ops.kernels.workspace import workspace
 
 
-def _ref_attn_fwd(q, k, v, kv_len, causal, scale):
+def attn_keep_scale(p: float, seed: int, offset: int, B: int, H: int, Lq: int, Lk: int):
+    """The attention-dropout multiplier keep / (1 - p) [B, H, Lq, Lk] (f32, CPU)
+    of the DROP kernels (csrc/kernels/attn_impl.h): element ((b H + h) Lq + q)
+    Lk8 + k of the Philox stream (seed, offset), Lk8 = 8 ceil(Lk / 8)."""
+    Lk8 = -(-Lk // 8) * 8
+    keep = philox.keep_mask(seed, offset, B * H * Lq * Lk8, p).view(B, H, Lq, Lk8)[..., :Lk]
+    return keep.to(torch.float32) / (1.0 - p)
+
+
+def _drop_args(drop):
+    """drop = (p, seed, ctr, site) or None -> the bindings' trailing arguments
+    (none when off: the call without the argument)."""
+    if drop is None or drop[0] <= 0:
+        return ()
+    p, seed, ctr, site = drop
+    return (float(p), int(seed), ctr, int(site))
+
+
+def _ref_attn_fwd(q, k, v, kv_len, causal, scale, keep_scale=None):
     """q [B,Lq,H,hd] ... -> out [B,Lq,H,hd], probs [B,H,Lq,Lk]. Masked logits
-    get -1e9 added exactly as the reference does (transformer_model.py:101-102)."""
+    get -1e9 added exactly as the reference does (transformer_model.py:101-102).
+    keep_scale (attn_keep_scale): attention dropout, out = (probs * keep_scale)
+    V; probs stay the undropped softmax."""
     s = torch.einsum("bqhd,bkhd->bhqk", q, k) * scale
     B, H, Lq, Lk = s.shape
     mask = torch.zeros(B, 1, Lq, Lk, dtype=s.dtype, device=s.device)
@@ -24,15 +45,19 @@ def _ref_attn_fwd(q, k, v, kv_len, causal, scale):
         qs = torch.arange(Lq, device=s.device)
         mask = torch.maximum(mask, (keys.view(1, Lk) > qs.view(Lq, 1)).to(s.dtype).view(1, 1, Lq, Lk))
     p = torch.softmax(s + mask * -1e9, dim=-1)
-    out = torch.einsum("bhqk,bkhd->bqhd", p, v)
+    pd = p if keep_scale is None else p * keep_scale.to(p.dtype)
+    out = torch.einsum("bhqk,bkhd->bqhd", pd, v)
     return out, p
 
 
-def attn_fwd(q, k, v, kv_len, scale: float, causal: bool):
+def attn_fwd(q, k, v, kv_len, scale: float, causal: bool, drop=None):
+    """drop = (p, seed, ctr, site): attention dropout at rate p from the Philox
+    stream (seed, ctr, site) (attn_impl.h; bf16, the register-staged kernels);
+    None or p = 0: off."""
     B, Lq, H, hd = q.shape
     out = torch.empty(B, Lq, H, hd, dtype=torch.bfloat16, device=q.device)
     lse = torch.empty(B, H, Lq, dtype=torch.float32, device=q.device)
-    C().attn_fwd(q, k, v, out, lse, kv_len, scale, causal)
+    C().attn_fwd(q, k, v, out, lse, kv_len, scale, causal, *_drop_args(drop))
     return out, lse
 
 
@@ -79,9 +104,10 @@ def attn_fwd_fp8(q8, k8, v8, sq, sk, sv, kv_len, scale: float, causal: bool, o8=
     return out, lse
 
 
-def attn_bwd(q, k, v, o, dout, lse, dq, dk, dv, kv_len, scale: float, causal: bool):
+def attn_bwd(q, k, v, o, dout, lse, dq, dk, dv, kv_len, scale: float, causal: bool, drop=None):
+    """drop: the forward's (attn_fwd); o is the dropped forward's output."""
     delta = workspace("attn_delta", lse.numel(), q.device)[: lse.numel()]
-    C().attn_bwd(q, k, v, o, dout, lse, delta, dq, dk, dv, kv_len, scale, causal)
+    C().attn_bwd(q, k, v, o, dout, lse, delta, dq, dk, dv, kv_len, scale, causal, *_drop_args(drop))
 
 
 # the fused backward of <= 128-token attention computes dO = dY @ Wo[:, head]
@@ -89,13 +115,15 @@ def attn_bwd(q, k, v, o, dout, lse, dq, dk, dv, kv_len, scale: float, causal: bo
 ATTN_BWD_FDO = os.environ.get("TDG_ATTN_BWD_FDO", "1") != "0"
 
 
-def attn_bwd_fdo(q, k, v, o, dy2, wo, lse, dq, dk, dv, kv_len, scale: float, causal: bool) -> bool:
+def attn_bwd_fdo(q, k, v, o, dy2, wo, lse, dq, dk, dv, kv_len, scale: float, causal: bool,
+                 drop=None) -> bool:
     """attn_bwd with dout = (dy2 @ wo).view(q.shape) computed in-kernel; False
-    (nothing launched) when not covered (Lq / Lk > 128, hd != 64)."""
+    (nothing launched) when not covered (Lq / Lk > 128, hd != 64). drop: as attn_bwd."""
     if not ATTN_BWD_FDO:
         return False
     delta = workspace("attn_delta", lse.numel(), q.device)[: lse.numel()]
-    return C().attn_bwd_fdo(q, k, v, o, dy2, wo, lse, delta, dq, dk, dv, kv_len, scale, causal)
+    return C().attn_bwd_fdo(q, k, v, o, dy2, wo, lse, delta, dq, dk, dv, kv_len, scale, causal,
+                            *_drop_args(drop))
 
 
 def attn_bwd_g8_ok(Lq: int, Lk: int, hd: int) -> bool:

@@ -53,7 +53,8 @@ import torch.distributed as dist
 
 from tensorflow_distributed_on_gke_amd.checkpoint import bundle
 from tensorflow_distributed_on_gke_amd.checkpoint.uploader import ModelUploader, make_storage
-from tensorflow_distributed_on_gke_amd.config import (Settings, check_accum_steps, check_batch_tokens,
+from tensorflow_distributed_on_gke_amd.config import (Settings, check_accum_steps,
+                                                      check_attention_dropout, check_batch_tokens,
                                                       check_distill, check_rdrop)
 from tensorflow_distributed_on_gke_amd.data.synthetic import SyntheticPairs
 from tensorflow_distributed_on_gke_amd.models.layers import RunCtx
@@ -76,6 +77,7 @@ def build_model(s: Settings, device, preset: Optional[str] = None) -> Transforme
             if getattr(s, k) is not None and preset is None}
     cfg = model_config(preset or s.preset, src_vocab=s.src_vocab, tgt_vocab=s.tgt_vocab, dropout=s.dropout,
                        label_smoothing=s.label_smoothing,
+                       attention_dropout=check_attention_dropout(s.attention_dropout, s.dtype),
                        max_src_len=max(s.max_len, s.src_len), max_tgt_len=max(s.max_len, s.tgt_len + 1),
                        **over)
     return Transformer(cfg).build(device, seed=s.seed)

@@ -26,7 +26,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
-from tensorflow_distributed_on_gke_amd.config import check_accum_steps, check_rdrop
+from tensorflow_distributed_on_gke_amd.config import (check_accum_steps, check_attention_dropout,
+                                                      check_rdrop)
 from tensorflow_distributed_on_gke_amd.models.layers import RunCtx, WgradQueue
 from tensorflow_distributed_on_gke_amd.models.transformer import Transformer
 from tensorflow_distributed_on_gke_amd.parallel.ddp import DataParallel
@@ -134,9 +135,12 @@ class TrainStep:
         self._ntok_reduce = ddp.all_reduce_async if multi else None
         # the micro-batch now running is its update's last (or only) one
         self.last_micro = True
+        # (the model's attention dropout: refused with fp8, whose attention has no dropout variant)
+        attn_dropout = check_attention_dropout(model.cfg.attention_dropout,
+                                               "fp8" if fp8_state is not None else "bf16")
         self.rt = RunCtx(training=True, dropout=model.cfg.dropout if dropout is None else dropout,
                          seed=seed, ctr=torch.zeros(1, dtype=torch.int64, device=dev),
-                         store=model.store, fp8=fp8_state)
+                         store=model.store, fp8=fp8_state, attn_dropout=attn_dropout)
         # weight gradients grouped per shape (layers.WgradQueue): at the end of
         # backward on one GPU; with data parallelism also at the decoder /
         # encoder boundary so the decoder-side buckets' all-reduce overlaps
