@@ -477,6 +477,63 @@ void attn_probs(const Tensor& q, const Tensor& k, const Tensor& probs,
             "tdg attn_probs");
 }
 
+// Head-mean alignment of cross-attention (attn_align.hip): hard int32 [B, Lq],
+// conf f32 [B, Lq], soft f32 [B, Lq, round8(Lk)] or none
+void attn_align(const Tensor& q, const Tensor& k, const Tensor& kv_len, const optional<Tensor>& q_len,
+                const Tensor& hard, const Tensor& conf, const optional<Tensor>& soft, double scale,
+                int64_t k_lo, int64_t k_trim) {
+  tdg::AttnAlignArgs a{};
+  a.xcd = attn_xcd();
+  for (auto* t : {&q, &k}) {
+    check_bf16(*t, "q/k");
+    TORCH_CHECK(t->dim() == 4 && t->stride(3) == 1, "q/k must be [B,L,H,hd] with hd contiguous");
+  }
+  a.B = (int)q.size(0);
+  a.Lq = (int)q.size(1);
+  a.H = (int)q.size(2);
+  a.Lk = (int)k.size(1);
+  a.ldk = (int)round8(a.Lk);
+  TORCH_CHECK(k.size(0) == a.B && k.size(2) == a.H && k.size(3) == q.size(3) && k.device() == q.device(),
+              "attn_align: q/k shape mismatch");
+  a.q = (const uint16_t*)q.data_ptr();
+  a.q_sb = q.stride(0); a.q_sl = q.stride(1); a.q_sh = (int)q.stride(2);
+  a.k = (const uint16_t*)k.data_ptr();
+  a.k_sb = k.stride(0); a.k_sl = k.stride(1); a.k_sh = (int)k.stride(2);
+  check_rows_aligned(q, 16, "attn_align q");
+  check_rows_aligned(k, 16, "attn_align k");
+  TORCH_CHECK(kv_len.is_cuda() && kv_len.device() == q.device(), "attn_align: kv_len on q's device");
+  a.kv_len = kv_len_ptr(kv_len, a.B);
+  if (q_len.has_value()) {
+    TORCH_CHECK(q_len->is_cuda() && q_len->device() == q.device() && q_len->scalar_type() == at::kInt &&
+                    q_len->numel() == a.B,
+                "q_len: int32 [B] on q's device");
+    a.q_len = q_len->data_ptr<int>();
+  }
+  TORCH_CHECK(hard.is_cuda() && hard.scalar_type() == at::kInt && hard.is_contiguous() &&
+                  hard.numel() == (int64_t)a.B * a.Lq && hard.device() == q.device(),
+              "hard must be a contiguous int32 [B,Lq]");
+  check_f32(conf, "conf");
+  check_contig(conf, "conf");
+  TORCH_CHECK(conf.numel() == (int64_t)a.B * a.Lq && conf.device() == q.device(), "conf must be [B,Lq]");
+  a.hard = hard.data_ptr<int>();
+  a.conf = conf.data_ptr<float>();
+  if (soft.has_value()) {
+    check_f32(*soft, "soft");
+    check_contig(*soft, "soft");
+    check_aligned(*soft, 16, "soft");
+    TORCH_CHECK(soft->numel() == (int64_t)a.B * a.Lq * a.ldk && soft->device() == q.device(),
+                "soft must be [B,Lq,8*ceil(Lk/8)]");
+    a.soft = soft->data_ptr<float>();
+  }
+  TORCH_CHECK(k_lo >= 0 && k_trim >= 0 && k_lo <= (1 << 20) && k_trim <= (1 << 20),
+              "attn_align: k_lo / k_trim out of range");
+  a.scale = (float)scale;
+  a.k_lo = (int)k_lo;
+  a.k_trim = (int)k_trim;
+  c10::DeviceGuard g(q.device());
+  check_err(tdg_attn_align(&a, (int)q.size(3), stream_of(q)), "tdg attn_align");
+}
+
 std::vector<int64_t> attn_last_plan() {
   int p[5];
   tdg_attn_last_plan(p);
@@ -499,5 +556,6 @@ void def_attention(py::module_& m) {
   m.def("attn_bwd_g8", &attn_bwd_g8);
   m.def("attn_bwd_f8", &attn_bwd_f8);
   m.def("attn_probs", &attn_probs);
+  m.def("attn_align", &attn_align);
   m.def("attn_last_plan", &attn_last_plan);
 }

@@ -59,6 +59,11 @@ int tdg_attn_bwd_f8(const tdg::AttnArgs* a, int hd, hipStream_t st);
 // or 0. family -1: none yet. The fp8 launchers do not record. Host only.
 void tdg_attn_last_plan(int out[5]);
 
+// ---------------------------------------------------------------- attn_align.hip
+// -1: hd not 16 / 32 / 64 / 128; -2: Lk > 1024; -3: 16 rows of Q (all heads)
+// with the row statistics over 64 KiB of LDS; nothing launched
+int tdg_attn_align(const tdg::AttnAlignArgs* a, int hd, hipStream_t st);
+
 // ---------------------------------------------------------------- decode.hip
 // -1: hd not 16 / 64 (decode_attn), beam outside [1, 8] or V outside
 // [1, 65536] (beam_topk, sample_token, ensemble_logprobs, score_tokens), M

@@ -98,4 +98,23 @@ struct QkvAttnArgs {
   // [B * L, d]); K / V are a.k / a.v (the batched K|V projection), Lk = a.Lk
   int cross;
 };
+
+// Head-mean cross-attention alignment (attn_align.hip attn_align_kernel):
+// A[i, j] = (1 / H) sum_h softmax_j(scale q_h[i] . k_h[j]) over j < kv_len[b]
+struct AttnAlignArgs {
+  const uint16_t* q;  // [B, Lq, H, hd] bf16 view (hd contiguous, 16-byte rows)
+  const uint16_t* k;  // [B, Lk, H, hd]
+  const int* kv_len;  // [B] valid keys (clamped to [0, Lk])
+  const int* q_len;   // [B] valid query rows, or null (all Lq)
+  int* hard;          // [B, Lq] arg-max of A over k_lo <= j < kv_len - k_trim (lowest j on ties), -1 if empty
+  float* conf;        // [B, Lq] A[i, hard], 0 where hard is -1
+  float* soft;        // [B, Lq, ldk] A (zeros past kv_len and in rows >= q_len), or null
+  long long q_sb, q_sl, k_sb, k_sl;
+  int q_sh, k_sh;
+  int B, H, Lq, Lk;
+  int ldk;  // 8 ceil(Lk / 8)
+  float scale;
+  int k_lo, k_trim;
+  int xcd;  // workgroup order, as AttnArgs::xcd
+};
 }  // namespace tdg

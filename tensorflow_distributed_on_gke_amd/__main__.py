@@ -4,10 +4,12 @@
     python -m tensorflow_distributed_on_gke_amd test  --weights PREFIX [PREFIX ...] [--ensemble-weights W ...]
             [--ema] [--sentence TEXT ...] [--beam N]
             [--sample N --temperature T --top-k K --top-p P --seed S] [--mbr [--mbr-utility bleu|chrf]]
-            [--input FILE --output FILE [--batch N] [--n-best]]
+            [--input FILE --output FILE [--batch N] [--n-best] [--align]]
     python -m tensorflow_distributed_on_gke_amd score --weights PREFIX [PREFIX ...] [--ensemble-weights W ...]
             [--ema] --input FILE --output FILE [--batch N] [--tokens] [--accuracy]
             [--rerank [--length-penalty A] [--mix L]]
+    python -m tensorflow_distributed_on_gke_amd align --weights PREFIX [--ema] --input FILE --output FILE
+            [--layer N] [--tokens] [--min-conf C] [--batch N]
     python -m tensorflow_distributed_on_gke_amd mbr   --input FILE --output FILE [--lc] [--utility bleu|chrf]
     python -m tensorflow_distributed_on_gke_amd bleu  --hyp FILE --ref FILE [--hyp-field K] [--ref-field K] [--lc]
     python -m tensorflow_distributed_on_gke_amd chrf  --hyp FILE --ref FILE [--hyp-field K] [--ref-field K] [--lc]
@@ -56,6 +58,18 @@ the model's first choice. With --rerank it writes one line per run of lines
 with equal source: the one that maximises logprob / ((5 + n_tok) / 6) ** A +
 L * the third input field (A default 0.6, as `test`; L default 0), ties to the
 first, with that key as its third field.
+`align` is word alignment from cross-attention (infer/align.py): for
+source<TAB>target[<TAB>...] lines (the output of `test --input` is such a file)
+it writes source<TAB>target<TAB>alignment, the alignment Pharaoh pairs `s-t`
+(source word - target word, 0-based, whitespace-separated words for the byte
+tokenizer, `##`-joined pieces for WordPiece) ascending by t: every target word
+with the source word its most confident piece attends to most, by the mean over
+heads of decoder layer --layer N's cross-attention (1-based; default the second
+to last). --tokens gives the tokenizers' piece indices instead; --min-conf C
+drops links whose head-mean probability is below C. Of several --weights only
+the first model's attention is read. `test --input ... --align` appends the
+same field to the lines it writes, from one teacher-forced pass over (source,
+hypothesis) after decoding.
 `mbr` is the same selection on text, without a model: of every run of
 source<TAB>candidate[<TAB>...] lines with equal source it writes
 source<TAB>best candidate<TAB>expected utility, ties to the first; the units are
@@ -191,11 +205,18 @@ def cmd_test(args) -> int:
         with open(args.input, encoding="utf-8") as f:
             lines = [line.rstrip("\n") for line in f]
         hyps = tester.translate_lines(lines, batch=args.batch, max_length=args.max_length, **mode)
+        fields = iter(())
+        if args.align:  # one teacher-forced pass over the hypotheses just decoded
+            from tensorflow_distributed_on_gke_amd.infer.align import pharaoh
+
+            flat = [(s, h[0]) for s, hs in zip(lines, hyps) for h in hs]
+            fields = iter(["\t" + pharaoh(a) for a in tester.align_pairs(
+                [s for s, _ in flat], [h for _, h in flat], batch=args.batch)])
         with open(args.output, "w", encoding="utf-8") as f:
             for s, hs in zip(lines, hyps):
                 for h, sc, *utility in hs:
                     f.write(f"{_flat(s)}\t{_flat(h)}\t{sc:.6f}" + "".join(f"\t{u:.6f}" for u in utility)
-                            + "\n")
+                            + next(fields, "") + "\n")
         print(f"{len(lines)} lines -> {args.output}")
         return 0
     text, tokens, attn = tester(list(args.sentence), max_length=args.max_length, **mode)
@@ -271,6 +292,23 @@ def cmd_score(args) -> int:
     if args.accuracy:
         msg += f", accuracy {hits / tokens if tokens else float('nan'):.6f}"
     print(msg + f" -> {args.output}")
+    return 0
+
+
+def cmd_align(args) -> int:
+    from tensorflow_distributed_on_gke_amd.infer.align import pharaoh
+
+    rows, _ = args.pairs
+    tester = _load_tester(args)
+    aligned = tester.align_pairs([r[0] for r in rows], [r[1] for r in rows], words=not args.tokens,
+                                 batch=args.batch, layer=args.layer)
+    links = 0
+    with open(args.output, "w", encoding="utf-8") as f:
+        for r, a in zip(rows, aligned):
+            field = pharaoh(a, args.min_conf)
+            links += len(field.split())
+            f.write(f"{_flat(r[0])}\t{_flat(r[1])}\t{field}\n")
+    print(f"{len(rows)} pairs, {links} links -> {args.output}")
     return 0
 
 
@@ -427,6 +465,20 @@ def main(argv=None) -> int:
                          "((5 + n_tok) / 6) ** A + L * third input field, that key third")
     sc.add_argument("--length-penalty", type=float, default=0.6, metavar="A")
     sc.add_argument("--mix", type=float, default=0.0, metavar="L")
+    e.add_argument("--align", action="store_true",
+                   help="with --input: a last field, the hypothesis' word alignment to the source "
+                        "(Pharaoh s-t pairs, as `align` writes)")
+    al = sub.add_parser("align", parents=[common, models])
+    al.add_argument("--input", default=None, metavar="FILE",
+                    help="source<TAB>target[<TAB>...] lines (the output of test --input is one)")
+    al.add_argument("--output", default=None, metavar="FILE",
+                    help="source<TAB>target<TAB>alignment lines, in input order")
+    al.add_argument("--layer", type=int, default=None, metavar="N",
+                    help="decoder layer whose cross-attention is read (1-based; default: second to last)")
+    al.add_argument("--tokens", action="store_true", help="piece indices instead of word indices")
+    al.add_argument("--min-conf", type=float, default=0.0, metavar="C",
+                    help="drop links whose head-mean attention is below C")
+    al.add_argument("--batch", type=int, default=32, help="pairs per batch")
     mb = sub.add_parser("mbr")
     mb.add_argument("--input", required=True, metavar="FILE",
                     help="source<TAB>candidate[<TAB>...] lines, a source's candidates on consecutive lines")
@@ -461,7 +513,7 @@ def main(argv=None) -> int:
     h = sub.add_parser("heartbeat")
     h.add_argument("--port", type=int, default=3479)
     args = ap.parse_args(argv)
-    if args.cmd in ("test", "score"):
+    if args.cmd in ("test", "score", "align"):
         if args.ema and not args.weights:
             ap.error(f"{args.cmd}: --ema needs --weights")
         if args.weights and len(args.weights) > 8:
@@ -482,7 +534,18 @@ def main(argv=None) -> int:
             args.pairs = _read_pairs(args.input, args.mix != 0.0)
         except (OSError, ValueError) as e:
             ap.error(f"score: {e}")
+    if args.cmd == "align":
+        if args.input is None or args.output is None:
+            ap.error("align: --input and --output are both needed")
+        if args.batch < 1 or (args.layer is not None and args.layer < 1):
+            ap.error("align: --batch and --layer must be at least 1")
+        try:  # before any model is built
+            args.pairs = _read_pairs(args.input, False)
+        except (OSError, ValueError) as e:
+            ap.error(f"align: {e}")
     if args.cmd == "test":
+        if args.align and not args.input:
+            ap.error("test: --align belongs to file mode (--input)")
         if (args.input is None) != (args.output is None) or (args.input and args.sentence):
             ap.error("test: --input and --output go together, without --sentence")
         if args.batch < 1:
@@ -515,7 +578,7 @@ def main(argv=None) -> int:
                      f"{len(args.ref_lines)}")
     if args.cmd == "test" and not args.sentence and not args.input:
         args.sentence = ["muitas pessoas vieram à estação."]  # reference test.py:9
-    return {"train": cmd_train, "test": cmd_test, "score": cmd_score, "mbr": cmd_mbr, "bleu": cmd_bleu,
+    return {"train": cmd_train, "test": cmd_test, "score": cmd_score, "align": cmd_align, "mbr": cmd_mbr, "bleu": cmd_bleu,
             "chrf": cmd_chrf,             "average": cmd_average, "heartbeat": cmd_heartbeat}[args.cmd](args)
 
 

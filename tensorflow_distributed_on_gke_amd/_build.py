@@ -61,7 +61,8 @@ def hip_flags(csrc: Path = CSRC) -> str:
 # packed f32 instructions (v_pk_add / mul / fma_f32); the older ones keep the
 # code they were measured and validated with.
 NO_PACKED_F32 = "-Xclang -target-feature -Xclang -packed-fp32-ops"
-HIP_EXTRA_FLAGS = {"beam_wide.hip": NO_PACKED_F32, "chrf.hip": NO_PACKED_F32, "rdrop.hip": NO_PACKED_F32}
+HIP_EXTRA_FLAGS = {"beam_wide.hip": NO_PACKED_F32, "chrf.hip": NO_PACKED_F32, "rdrop.hip": NO_PACKED_F32,
+                   "attn_align.hip": NO_PACKED_F32}
 
 
 def write_ninja() -> Path:

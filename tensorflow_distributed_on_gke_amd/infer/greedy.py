@@ -26,7 +26,8 @@ from tensorflow_distributed_on_gke_amd.ops.kernels.chrf import CHRF_MAX_L
 from tensorflow_distributed_on_gke_amd.infer.sample import sample_search
 from tensorflow_distributed_on_gke_amd.infer.score import score_pairs
 from tensorflow_distributed_on_gke_amd.infer.step import DecoderStep
-from tensorflow_distributed_on_gke_amd.infer.tokenizer import after_first_end
+from tensorflow_distributed_on_gke_amd.infer.align import Links, align_pairs, project_words
+from tensorflow_distributed_on_gke_amd.infer.tokenizer import ByteTokenizer, after_first_end, word_ids
 from tensorflow_distributed_on_gke_amd.models.layers import CrossKVFn, EmbedFn, KVGrad, RunCtx
 from tensorflow_distributed_on_gke_amd.models.transformer import PAD_ID, Transformer, seq_lengths
 
@@ -319,6 +320,51 @@ class Tester:
                 out[i] = (float(sent[j]), n, tok_lp[j, :n].tolist(),
                           top_lp[j, :n].tolist() if want_top else None)
         return out
+
+    def align_pairs(self, sources: Sequence[str], targets: Sequence[str], words: bool = True,
+                    batch: int = 32, layer: Optional[int] = None) -> List[Links]:
+        """Per (source, target) pair of text, in input order, its alignment
+        (infer/align.py): (target index, source index, conf) links ascending by
+        target, over words (`words`; whitespace-separated for the byte
+        tokenizer, `##`-joined pieces for WordPiece) or over the tokenizers'
+        pieces, special tokens not counted. A side longer than the model's
+        positional table is cut to it (the source keeps its [END]); an empty
+        target has no links. Of an ensemble, the first member's attention.
+        Pairs run `batch` at a time in order of (source length, target length)."""
+        if len(sources) != len(targets):
+            raise ValueError(f"{len(sources)} sources for {len(targets)} targets")
+        cfg = self.model.cfg
+        _, end = self.tgt_tok.start_end()
+        src_rows, tgt_rows = [], []
+        for s, t in zip(sources, targets):
+            r = self.src_tok.tokenize(s)[0]
+            r = r[r != PAD_ID]
+            if len(r) > cfg.max_src_len:
+                r = torch.cat([r[:cfg.max_src_len - 1], r[-1:]])
+            src_rows.append(r)
+            r = self.tgt_tok.tokenize(t)[0]
+            tgt_rows.append(r[r != PAD_ID][:cfg.max_tgt_len + 1])
+        order = sorted(range(len(sources)), key=lambda i: (len(src_rows[i]), len(tgt_rows[i]), i))
+        out: List[Links] = [[] for _ in sources]
+        for b0 in range(0, len(order), batch):
+            idx = order[b0:b0 + batch]
+            src = torch.zeros(len(idx), max(len(src_rows[i]) for i in idx), dtype=torch.int64)
+            tgt = torch.zeros(len(idx), max(len(tgt_rows[i]) for i in idx), dtype=torch.int64)
+            for j, i in enumerate(idx):
+                src[j, :len(src_rows[i])] = src_rows[i]
+                tgt[j, :len(tgt_rows[i])] = tgt_rows[i]
+            for i, links in zip(idx, align_pairs(self.model, src, tgt, layer=layer, end=end)):
+                if words:
+                    links = project_words(links, self._word_ids(self.tgt_tok, tgt_rows[i]),
+                                          self._word_ids(self.src_tok, src_rows[i]))
+                out[i] = links
+        return out
+
+    @staticmethod
+    def _word_ids(tok, row: torch.Tensor) -> List[int]:
+        """Word index per real token of a [START] .. row (the specials stripped)."""
+        ids = [t for t in row.tolist()[1:] if t != tok.start_end()[1]]
+        return word_ids(tok.lookup(ids), byte_level=isinstance(tok, ByteTokenizer))
 
     def _text(self, row: List[int]):
         """One decoded row -> (text, token names), cut after [END], PAD dropped."""

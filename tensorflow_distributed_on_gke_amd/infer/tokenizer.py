@@ -23,6 +23,27 @@ def after_first_end(tokens: torch.Tensor, end: int) -> torch.Tensor:
     return is_end.cumsum(dim=-1) - is_end > 0
 
 
+def word_ids(pieces: Sequence[str], byte_level: bool = False) -> List[int]:
+    """The word index of every piece of a tokenised text (infer/align.py's
+    projection to words), -1 for a piece that is part of no word. WordPiece
+    names: a `##` continuation piece belongs to the word before it, every other
+    piece starts one. byte_level (ByteTokenizer.lookup names): a word is a run
+    of non-whitespace bytes, whitespace is part of none."""
+    out, w, inside = [], -1, False
+    for p in pieces:
+        if byte_level:
+            if p in (" ", "\t", "\n", "\r", "\x0b", "\x0c"):  # (ASCII: a UTF-8 tail byte is never one)
+                inside = False
+                out.append(-1)
+                continue
+            w += 0 if inside else 1
+            inside = True
+        elif not (p.startswith("##") and w >= 0):
+            w += 1
+        out.append(w)
+    return out
+
+
 class ByteTokenizer:
     def __init__(self, vocab_size: int = 260):
         if vocab_size < OFFSET + 256:

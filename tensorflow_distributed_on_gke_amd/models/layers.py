@@ -55,7 +55,7 @@ from tensorflow_distributed_on_gke_amd.models.wgrad import (  # noqa: F401 (Wgra
     WgradQueue, _beta, _fold_bias_later, _fp8_grad_bias, _ready, _wgrad)
 from tensorflow_distributed_on_gke_amd.ops import kernels as K
 from tensorflow_distributed_on_gke_amd.ops import fp8, philox
-from tensorflow_distributed_on_gke_amd.ops.kernels.attention import _ref_attn_fwd, attn_keep_scale
+from tensorflow_distributed_on_gke_amd.ops.kernels.attention import _ref_attn_fwd, attn_align, attn_keep_scale
 
 LN_EPS = 1e-6
 
@@ -81,6 +81,10 @@ class RunCtx:
     emb_csr: Optional[dict] = None
     # dropout rate on the attention probabilities (training only; bf16)
     attn_dropout: float = 0.0
+    # inference probe: {cross-attention site: keyword arguments of
+    # ops.kernels.attention.attn_align (q_len, k_lo, k_trim, want_soft)}; the
+    # block replaces a requested site's entry by its (hard, conf, soft)
+    align: Optional[dict] = None
 
     @property
     def p(self) -> float:
@@ -163,8 +167,9 @@ def _f8_bwd_planned(rt: RunCtx, lean: bool, Lq: int, Lk: int, hd: int) -> bool:
     """Forward-time decision: will this (e4m3-forward) attention block's
     backward run on the fp8 kernel? Then the bf16 copies of its projection
     outputs are never read and not written. (Not with attention maps: they
-    read the bf16 Q / K.)"""
-    return (lean and fp8.ATTN_BWD_F8 and rt.attn_maps is None and K.attn_bwd_f8_ok(Lq, Lk, hd))
+    read the bf16 Q / K; nor with an alignment request.)"""
+    return (lean and fp8.ATTN_BWD_F8 and rt.attn_maps is None and rt.align is None
+            and K.attn_bwd_f8_ok(Lq, Lk, hd))
 
 
 # =============================================================================== LN helpers
@@ -435,7 +440,8 @@ def _attn_block_fwd(ctx, x, w_in: Param, b_in: Param, wo: Param, bo: Param, gamm
              if rt.fp8 is not None else None)
         proj, proj8 = (r[0], r[1]) if f8 and r is not None else (r, None)
         fused = None
-        if proj is None and not f8b and rt.fp8 is None and rt.attn_maps is None and drop is None:
+        if (proj is None and not f8b and rt.fp8 is None and rt.attn_maps is None and drop is None
+                and not (rt.align and site in rt.align)):
             # projection + attention forward in one launch (<= 128 tokens)
             fused = K.qkv_attn_fwd(x2, w_in.compute, b_in.master, B, heads, kv_len, scale, causal,
                                    *(kv or ()))
@@ -466,6 +472,10 @@ def _attn_block_fwd(ctx, x, w_in: Param, b_in: Param, wo: Param, bo: Param, gamm
         o, aux = _ref_attn_fwd(q, k, v, kv_len, causal, scale, ctx.attn_ks)
     if rt.attn_maps is not None:  # (_f8_bwd_planned: the bf16 q, k exist when maps are asked for)
         rt.attn_maps[site] = attention_probs(q, k, kv_len, causal, scale)
+    if rt.align and site in rt.align:  # (as the maps: off the fused launch, bf16 q and k exist)
+        klen = kv_len if kv_len is not None else torch.full((B,), k.shape[1], dtype=torch.int32,
+                                                            device=x.device)
+        rt.align[site] = attn_align(q, k, klen, scale, **rt.align[site])
     y = _attn_out_ln_fwd(ctx, o, x, wo, bo, gamma, beta, site, rt, kx, o8e)
     return y, x2, proj, o, aux
 

@@ -177,6 +177,76 @@ def attn_bwd_f8(q8, k8, v8, sq, sk, sv, o, do8, sdo, lse, kv_len, scale: float, 
     return q8.shape[0]
 
 
+ALIGN_MAX_LK = 1024  # attn_align.hip: a row's accumulators are registers
+
+
+def _ref_attn_align(q, k, kv_len, scale, q_len, k_lo, k_trim, want_soft, dt=torch.float32):
+    """attn_align's definition in torch (the CPU arm; dt float64: the tests'
+    reference): masked keys get probability exactly 0, ties go to the lowest key."""
+    B, Lq, H, _ = q.shape
+    Lk = k.shape[1]
+    ldk = -(-Lk // 8) * 8
+    dev = q.device
+    kvl = kv_len.to(dev).long().clamp(0, Lk).view(B, 1, 1)
+    ql = (q_len.to(dev).long().clamp(0, Lq) if q_len is not None
+          else torch.full((B,), Lq, dtype=torch.long, device=dev)).view(B, 1)
+    keys = torch.arange(Lk, device=dev).view(1, 1, Lk)
+    att = keys < kvl                                                      # [B, 1, Lk]
+    rows = torch.arange(Lq, device=dev).view(1, Lq) < ql                  # [B, Lq]
+    s = torch.einsum("bqhd,bkhd->bhqk", q.to(dt), k.to(dt)) * scale
+    s = s.masked_fill(~att.unsqueeze(1), -float("inf"))
+    m = s.max(-1, keepdim=True).values
+    e = torch.exp(s - torch.where(torch.isfinite(m), m, torch.zeros_like(m)))
+    l = e.sum(-1, keepdim=True)
+    A = (e / l.clamp_min(1e-300)).mean(1)                                 # [B, Lq, Lk]; kv_len 0: zeros
+    A = A * rows.unsqueeze(-1).to(dt)
+    rng = (keys >= k_lo) & (keys < kvl - k_trim)                          # [B, 1, Lk]
+    masked = torch.where(rng, A, torch.full_like(A, -1.0))
+    conf = masked.max(-1).values
+    # (torch.max may return any index among ties on some back ends: take the first explicitly)
+    first = (masked == conf.unsqueeze(-1)).to(torch.int64).argmax(-1)
+    ok = rows & (conf >= 0)
+    hard = torch.where(ok, first, torch.full_like(first, -1)).to(torch.int32)
+    conf = torch.where(ok, conf, torch.zeros_like(conf)).to(torch.float32)
+    soft = None
+    if want_soft:
+        soft = torch.zeros(B, Lq, ldk, dtype=torch.float32, device=dev)
+        soft[..., :Lk] = A.to(torch.float32)
+    return hard, conf, soft
+
+
+def attn_align(q, k, kv_len, scale: float, q_len=None, k_lo: int = 0, k_trim: int = 0,
+               want_soft: bool = False):
+    """Head-mean cross-attention alignment (csrc/kernels/attn_align.hip), one
+    launch. q [B, Lq, H, hd], k [B, Lk, H, hd] bf16 views; kv_len / q_len int32
+    [B]. With P_h = softmax_j(scale q_h k_h^T) over j < kv_len[b] and A = mean_h
+    P_h, returns
+      hard int32 [B, Lq]: argmax_j A[i, j] over k_lo <= j < kv_len[b] - k_trim
+                          (lowest j on ties; -1 when that range is empty or
+                          i >= q_len[b]),
+      conf f32 [B, Lq]:   A[i, hard] (0 where hard is -1),
+      soft f32 [B, Lq, 8 ceil(Lk / 8)] (want_soft) or None: A, zeros past
+                          kv_len[b] and in rows >= q_len[b].
+    The softmax always runs over all kv_len[b] keys; k_lo / k_trim narrow the
+    arg-max only. CPU tensors take the f32 torch arm of the same definition."""
+    B, Lq, H, hd = q.shape
+    Lk = k.shape[1]
+    if Lk > ALIGN_MAX_LK:
+        raise ValueError(f"attn_align: Lk {Lk} > {ALIGN_MAX_LK}")
+    if B * Lq * Lk == 0:  # (nothing to launch)
+        return (torch.full((B, Lq), -1, dtype=torch.int32, device=q.device),
+                torch.zeros(B, Lq, dtype=torch.float32, device=q.device),
+                torch.zeros(B, Lq, 0, dtype=torch.float32, device=q.device) if want_soft else None)
+    if not q.is_cuda:
+        return _ref_attn_align(q, k, kv_len, scale, q_len, k_lo, k_trim, want_soft)
+    hard = torch.empty(B, Lq, dtype=torch.int32, device=q.device)
+    conf = torch.empty(B, Lq, dtype=torch.float32, device=q.device)
+    soft = (torch.empty(B, Lq, -(-Lk // 8) * 8, dtype=torch.float32, device=q.device)
+            if want_soft else None)
+    C().attn_align(q, k, kv_len, q_len, hard, conf, soft, scale, k_lo, k_trim)
+    return hard, conf, soft
+
+
 def attn_probs(q, k, kv_len, scale: float, causal: bool) -> torch.Tensor:
     B, Lq, H, hd = q.shape
     Lk = k.shape[1]
